@@ -21,6 +21,13 @@ build-only and hash + build brackets, with the oracle restatement timed beside i
 calibration.
 
 `--gpus N` (N > 1) without torchrun starts the N ranks itself (launch_ranks).
+
+A plain run (`--gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps and prints
+the result line: value, ms_per_step and the build / probe split from the timed steps' own
+probe events. `--full` adds everything that takes work of its own: the per-kernel stage pass,
+the probe's measured floor, the roofline, the verification (every key found, image SHA-256s
+against tests/golden/sha256.json), the PCIe-inclusive rates, routed probes and the CPU
+baseline. `--dump-outputs DIR` writes what the last timed step computed (dump_outputs).
 """
 import argparse
 import hashlib
@@ -74,20 +81,33 @@ def parse():
     p.add_argument("--filters", type=int, default=0, help="override filters (per GPU for c2/c3)")
     p.add_argument("--keys-per-filter", type=int, default=0)
     p.add_argument("--log-index-size", type=int, default=8)
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also run everything beside the headline figure: per-kernel stage pass, probe floor, "
+                        "roofline, verification against the golden SHA-256s, PCIe-inclusive rates, "
+                        "--routed-probe, CPU baseline (each can be switched off below)")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="after the timed steps write what the last one computed (found_values, filter "
+                        "images, filter infos; block sums over all of it and a fixed seeded sample) as "
+                        "DIR/<name>.npy, float32/float64")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     p.add_argument("--cpu-threads", type=int, default=0,
                    help="CPU baseline threads (0 = every usable core: the affinity set capped by the cgroup quota)")
-    p.add_argument("--no-e2e", action="store_true")
+    p.add_argument("--no-e2e", action="store_true", help="with --full: skip the PCIe-inclusive rates")
     p.add_argument("--dist-always", action="store_true",
                    help="initialise torch.distributed (RCCL) and run every collective even with one rank: "
                         "exercises the multi-rank code path on a one-GPU box")
     p.add_argument("--routed-probe", action="store_true",
-                   help="also time routed probes: each rank probes keys of every rank's filters, "
+                   help="with --full, also time routed probes: each rank probes keys of every rank's filters, "
                         "moved to the owner by all-to-all (route.py); reported beside value")
     p.add_argument("--pmc", default=os.path.join(ROOT, "profiles", "pmc_r05.json"))
     p.add_argument("--digest-out", default="",
                    help="write each rank's per-filter image SHA-256s to <path>.rank<r> (tests)")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    if args.routed_probe and not args.full:
+        p.error("--routed-probe is a measurement beside the headline figure: give --full with it")
+    return args
 
 
 def stage_bytes(stage, N, P, image_bytes, slot_bytes, unique, key_bytes=None, probe_key_bytes=None):
@@ -198,6 +218,98 @@ def e2e_duplex(eng, cfg, stream, ins, h_ins, compute, found, batch, infos, n, F,
     return rate, ok
 
 
+DUMP_SEED = 0x0D0C5EED
+DUMP_SAMPLE = 1 << 20       # sampled found_values / image bytes
+DUMP_SLOT_SAMPLE = 1 << 18  # sampled index slots
+DUMP_FOUND_BLOCK = 1 << 16  # found_values per block sum
+DUMP_SLOT_BLOCK = 256       # index slots per block sum
+DUMP_MAX_BYTES = 64 << 20
+
+
+def _halves(v):
+    """uint64 values as two float64 arrays (low and high 32 bits): both exact"""
+    v = np.ascontiguousarray(v).view(np.uint64)
+    return (v & np.uint64(0xFFFFFFFF)).astype(np.float64), (v >> np.uint64(32)).astype(np.float64)
+
+
+def _pick(rng, size, k):
+    """k seeded positions of `size` in ascending order, or all of them when there are no more"""
+    return np.arange(size) if size <= k else np.sort(rng.integers(0, size, size=k))
+
+
+def _block_sums(x, block):
+    """torch int64 values < 2^32 summed per `block` consecutive ones (the tail is its own block)"""
+    m = x.numel() // block * block
+    parts = [x[:m].view(-1, block).sum(1)]
+    if m < x.numel():
+        parts.append(x[m:].sum().reshape(1))
+    return torch.cat(parts).cpu().numpy().astype(np.float64)
+
+
+def dump_outputs(path, rank, world, batch, F, page_size, found=None):
+    """--dump-outputs: what a caller of the timed path holds after its last step -- the probe's
+    found_values and every filter's info, pages and index slots -- as <path>/<name>.npy
+    (<name>.rank<r>.npy with several ranks), float32 / float64, every value exact:
+      filter_info        (F, 6): num_fingerprints, num_unique, value_size, num_indices, num_pages, error
+      page_sums          per 4-KiB page, filters in order: the sum of the page's uint32 words
+      page_bytes_sample  DUMP_SAMPLE page bytes (as many per filter, seeded positions, in order)
+                         -- here and below the whole output where it is no larger than the sample
+      slot_sums_lo/hi    sums of the low / high 32 bits of DUMP_SLOT_BLOCK consecutive index slots
+      slots_sample_lo/hi DUMP_SLOT_SAMPLE index slots, low / high 32 bits
+      found_sums_lo/hi   sums of the low / high 32 bits of DUMP_FOUND_BLOCK consecutive found_values
+      found_sample_lo/hi DUMP_SAMPLE found_values, low / high 32 bits
+    The sums cover every byte of the outputs; the samples keep single values comparable. The
+    sampled positions depend only on the seed and the outputs' sizes, so two builds given the
+    same arguments write comparable files."""
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    out = {}
+    infos = batch.infos()
+    out["filter_info"] = np.array([[i.num_fingerprints, i.num_unique, i.value_size, i.num_indices, i.num_pages,
+                                    i.error] for i in infos], dtype=np.float64).reshape(F, 6)
+    page_sums, page_sample, slots = [], [], []
+    per_filter = max(1, DUMP_SAMPLE // F)
+    for f in range(F):
+        if infos[f].error:
+            continue  # no image to read; filter_info carries the error bits
+        img = batch.image(f)
+        words = img.pages.view(np.uint32).reshape(img.num_pages, page_size // 4)
+        page_sums.append(words.sum(axis=1, dtype=np.uint64).astype(np.float64))
+        page_sample.append(img.pages[_pick(rng, img.pages.size, per_filter)])
+        slots.append(img.slots)
+    out["page_sums"] = np.concatenate(page_sums) if page_sums else np.zeros(0)
+    out["page_bytes_sample"] = (np.concatenate(page_sample) if page_sample else np.zeros(0)).astype(np.float32)
+    slots = np.concatenate(slots) if slots else np.zeros(0, dtype=np.uint64)
+    lo, hi = _halves(slots)
+    edges = np.arange(0, slots.size, DUMP_SLOT_BLOCK)
+    out["slot_sums_lo"] = np.add.reduceat(lo, edges) if slots.size else lo
+    out["slot_sums_hi"] = np.add.reduceat(hi, edges) if slots.size else hi
+    if slots.size:
+        pick = _pick(rng, slots.size, DUMP_SLOT_SAMPLE)
+        out["slots_sample_lo"], out["slots_sample_hi"] = lo[pick], hi[pick]
+    if found is not None and found.numel():
+        out["found_sums_lo"] = _block_sums(found & 0xFFFFFFFF, DUMP_FOUND_BLOCK)
+        out["found_sums_hi"] = _block_sums((found >> 32) & 0xFFFFFFFF, DUMP_FOUND_BLOCK)
+        pick = torch.from_numpy(_pick(rng, found.numel(), DUMP_SAMPLE)).to(found.device)
+        out["found_sample_lo"], out["found_sample_hi"] = _halves(found[pick].cpu().numpy())
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs: {total} bytes"
+    sfx = f".rank{rank}" if world > 1 else ""
+    for name, a in out.items():
+        np.save(os.path.join(path, f"{name}{sfx}.npy"), a)
+
+
+def write_digests(path, rank, batch, F, filter_begin):
+    """--digest-out: per-filter image digests of this rank (the multi-rank tests compare them
+    with a single-process build of the same filters)"""
+    dig = {}
+    for f in range(F):
+        img = batch.image(f)
+        dig[filter_begin + f] = hashlib.sha256(img.pages.tobytes() + img.slots.tobytes()).hexdigest()
+    with open(f"{path}.rank{rank}", "w") as fh:
+        json.dump(dig, fh)
+
+
 def main():
     args = parse()
     spawned = launch_ranks(args)
@@ -301,18 +413,60 @@ def main():
     elapsed = time.perf_counter() - t0
     for back in range(args.steps):  # the probe's HIP events of every timed step, on its stream
         stages["probe"].append(batch.timings(back)["probe"])
-    # per-kernel build stages: a short pass with an event between every kernel (not timed)
-    diag = min(args.steps, 5)
-    batch.set_timing(True, sets=diag)
-    for _ in range(diag):
-        step()
-    stream.synchronize()
-    for back in range(diag):
-        for k, v in batch.timings(back).items():
-            if k != "probe":
-                stages[k].append(v)
+    if args.dump_outputs:  # the last timed step's results, before anything below runs over them
+        dump_outputs(args.dump_outputs, rank, world, batch, F, cfg.page_size, found)
+    if args.full:
+        # per-kernel build stages: a short pass with an event between every kernel (not timed)
+        diag = min(args.steps, 5)
+        batch.set_timing(True, sets=diag)
+        for _ in range(diag):
+            step()
+        stream.synchronize()
+        for back in range(diag):
+            for k, v in batch.timings(back).items():
+                if k != "probe":
+                    stages[k].append(v)
     elapsed = S.max_over_ranks(elapsed, dist, coll_dev)
     keys_all = S.sum_over_ranks(float(N), dist, coll_dev)
+    ms_per_step = elapsed / args.steps * 1e3
+    # the timed step minus its probe (launch gaps included); with --full the stage pass's
+    # event-bracketed build_total is reported beside it in `kernels`
+    probe_ms = float(np.mean(stages["probe"]))
+    build_ms = ms_per_step - probe_ms
+    value = keys_all / (elapsed / args.steps) / 1e6
+    out = {
+        "metric": METRIC,
+        "value": round(value, 1),
+        "unit": "Mkeys/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 3),
+        "higher_is_better": True,
+        "scaling": scaling,
+        "vs_baseline": None,
+        "dtype": "u32",
+        "data": ("synthetic: variable-length 8-100 B keys (splitmix64), Zipf(0.99) probe mix, copied to HBM "
+                 "before timing" if var else
+                 "synthetic: sequential-id 24 B keys (filter_test format), generated in HBM"),
+        "config": {"workload": wdesc, "filters_total": F_total,
+                   "filters_per_gpu": F, "keys_per_filter": n, "key_len": "8-100" if var else 24,
+                   "fingerprint_size": 26, "log_index_size": args.log_index_size, "seed": 42,
+                   "parallelism": f"key-range shards, {world} rank(s), no data-path collective"},
+        "build_mkeys_s": round(keys_all / (build_ms * 1e-3) / 1e6, 1),
+        "probe_mkeys_s": round(S.sum_over_ranks(float(P), dist, coll_dev) / (probe_ms * 1e-3) / 1e6, 1),
+        "full": args.full,
+    }
+    if not args.full:
+        # a plain run ends here: the headline figure and the split its own probe events give
+        if args.digest_out:
+            write_digests(args.digest_out, rank, batch, F, me.filter_begin)
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        batch.close()
+        if dist is not None:
+            dist.destroy_process_group()
+        return
 
     # ---- verification (outside the timed region) -------------------------------------
     if var:
@@ -356,14 +510,7 @@ def main():
                 verified = verified and good
                 sha_checked.append(g)
     if args.digest_out:
-        # per-filter image digests of this rank (the multi-rank tests compare them with a
-        # single-process build of the same filters)
-        dig = {}
-        for f in range(F):
-            img = batch.image(f)
-            dig[me.filter_begin + f] = hashlib.sha256(img.pages.tobytes() + img.slots.tobytes()).hexdigest()
-        with open(f"{args.digest_out}.rank{rank}", "w") as fh:
-            json.dump(dig, fh)
+        write_digests(args.digest_out, rank, batch, F, me.filter_begin)
 
     # ---- end-to-end (PCIe-inclusive) rate, reported beside `value` (never as it) ------
     # keys H2D from pinned host memory -> build -> probe -> found_values + page images +
@@ -515,33 +662,7 @@ def main():
             traffic = pm.get("per_launch_hbm_bytes", {}).get(dom)
         except Exception:
             traffic = None
-    ms_per_step = elapsed / args.steps * 1e3
-    # the timed step minus its probe (launch gaps included); the stage pass's event-bracketed
-    # build_total is reported beside it in `kernels`
-    probe_ms = ms["probe"]
-    build_ms = ms_per_step - probe_ms
-    value = keys_all / (elapsed / args.steps) / 1e6
-    out = {
-        "metric": METRIC,
-        "value": round(value, 1),
-        "unit": "Mkeys/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 3),
-        "higher_is_better": True,
-        "scaling": scaling,
-        "vs_baseline": None,
-        "dtype": "u32",
-        "data": ("synthetic: variable-length 8-100 B keys (splitmix64), Zipf(0.99) probe mix, copied to HBM "
-                 "before timing" if var else
-                 "synthetic: sequential-id 24 B keys (filter_test format), generated in HBM"),
-        "config": {"workload": wdesc, "filters_total": F_total,
-                   "filters_per_gpu": F, "keys_per_filter": n, "key_len": "8-100" if var else 24,
-                   "fingerprint_size": 26, "log_index_size": args.log_index_size, "seed": 42,
-                   "parallelism": f"key-range shards, {world} rank(s), no data-path collective"},
-        "build_mkeys_s": round(keys_all / (build_ms * 1e-3) / 1e6, 1),
-        "probe_mkeys_s": round(S.sum_over_ranks(float(P), dist, coll_dev) / (probe_ms * 1e-3) / 1e6, 1),
+    out.update({
         "e2e_pcie_mkeys_s": round(e2e, 1) if e2e else None,
         "e2e_pcie_serial_mkeys_s": round(e2e_serial, 1) if e2e else None,
         "e2e_pcie_hashes_mkeys_s": round(e2e_h, 1) if e2e_h else None,
@@ -560,7 +681,7 @@ def main():
         "build_total_stage_pass_ms": round(ms["build_total"], 4),
         "verified": verified,
         "sha_checked_filters": sha_checked,
-    }
+    })
     if routed is not None:
         out["routed_probe"] = routed
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
@@ -673,7 +794,32 @@ def run_compaction(args, rank, world, dist, dev, coll_dev, backend):
     keys_job = S.sum_over_ranks(float(F * n * V), dist, coll_dev)
     walls /= steps
     builds /= steps
+    if args.dump_outputs:  # the last timed chain's final filters
+        dump_outputs(args.dump_outputs, rank, world, last, F, cfg.page_size)
     last.close()
+    ms_step = elapsed / steps * 1e3
+    value = keys_job / (elapsed / steps) / 1e6
+    out = {
+        "metric": "routing_filter compaction chain: new keys/s through create + incremental build + release, device-resident",
+        "value": round(value, 1), "unit": "Mkeys/s", "n_gpus": world, "steps": steps, "warmup": args.warmup,
+        "ms_per_step": round(ms_step, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "u32",
+        "data": "synthetic: filter_test-format 24 B keys (f << 32) + (v + 1) j, generated in HBM",
+        "config": {"workload": WORKLOADS["compaction"][3], "filters_per_gpu": F, "rounds": V,
+                   "keys_per_round": n, "fingerprints_final": V * n, "fingerprint_size": 26,
+                   "log_index_size": args.log_index_size, "seed": 42,
+                   "parallelism": f"filter shards, {world} rank(s), no data-path collective"},
+        "round_wall_ms": [round(x, 3) for x in walls],
+        "round_build_ms": [round(x, 3) for x in builds],
+        "full": args.full,
+    }
+    if not args.full:
+        # a plain run ends here: the timed chains' own figures
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
 
     # per-stage times of one chain's rounds (HIP events), outside the timed loop
     lastd, _, _, _ = chain(False, timing=True)
@@ -761,20 +907,7 @@ def run_compaction(args, rank, world, dist, dev, coll_dev, backend):
     achieved = alg_all / (S.max_over_ranks(b_ms, dist, coll_dev) * 1e-3) / 1e9
     peak = HBM_PEAK_GBS * world
     readback_bytes = sum(i.num_pages * pg + i.num_indices * 8 for inf in infos_all for i in inf)
-    ms_step = elapsed / steps * 1e3
-    value = keys_job / (elapsed / steps) / 1e6
-    out = {
-        "metric": "routing_filter compaction chain: new keys/s through create + incremental build + release, device-resident",
-        "value": round(value, 1), "unit": "Mkeys/s", "n_gpus": world, "steps": steps, "warmup": args.warmup,
-        "ms_per_step": round(ms_step, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "u32",
-        "data": "synthetic: filter_test-format 24 B keys (f << 32) + (v + 1) j, generated in HBM",
-        "config": {"workload": WORKLOADS["compaction"][3], "filters_per_gpu": F, "rounds": V,
-                   "keys_per_round": n, "fingerprints_final": V * n, "fingerprint_size": 26,
-                   "log_index_size": args.log_index_size, "seed": 42,
-                   "parallelism": f"filter shards, {world} rank(s), no data-path collective"},
-        "round_wall_ms": [round(x, 3) for x in walls],
-        "round_build_ms": [round(x, 3) for x in builds],
+    out.update({
         "with_readback": {"mkeys_s": round(keys_job / tr / 1e6, 1), "chain_ms": round(tr * 1e3, 3),
                           "round_wall_ms": [round(x, 3) for x in rb_walls],
                           "readback_gb_per_chain": round(readback_bytes / 1e9, 3),
@@ -787,7 +920,7 @@ def run_compaction(args, rank, world, dist, dev, coll_dev, backend):
         "verified": verified, "sha_checked_filters": sha_checked,
         "num_unique_filter0": int(final[0].num_unique),
         "dropin_latency": dropin,
-    }
+    })
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import cpu_baseline as CB
         cb = CB.chain(args.log_index_size, V, n, threads=args.cpu_threads)

@@ -110,7 +110,7 @@ def test_bench_compaction_full_chains_golden(gpus, filters):
     final filters, and filters 0 and 1 equal the reference's chains byte for byte (filter 0
     is filter_test's basic chain: num_unique 4,254,486)"""
     line = _bench(["--workload", "compaction", "--gpus", str(gpus), "--filters", str(filters),
-                   "--steps", "1", "--warmup", "0", "--no-cpu-baseline"])
+                   "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline"])
     assert line["verified"], line
     assert line["n_gpus"] == gpus
     assert 0 in line["sha_checked_filters"]

@@ -178,7 +178,7 @@ def test_bench_two_ranks_equal_one_process(tmp_path, workload, filters):
     weak (2 filters per rank = 4 in all)."""
     n = 1 << 16
     common = ["--workload", workload, "--keys-per-filter", str(n), "--steps", "2", "--warmup", "1",
-              "--no-cpu-baseline", "--no-e2e"]
+              "--full", "--no-cpu-baseline", "--no-e2e"]
     d2 = str(tmp_path / "two")
     d1 = str(tmp_path / "one")
     line2 = _bench(common + ["--gpus", "2", "--filters", str(filters), "--digest-out", d2], {})

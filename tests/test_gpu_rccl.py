@@ -125,7 +125,7 @@ def test_router_all_to_all_over_rccl_one_rank():
 
 def test_bench_multi_rank_path_over_rccl_one_rank():
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--dist-always", "--filters", "2", "--keys-per-filter",
-           "300000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-e2e", "--routed-probe",
+           "300000", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-e2e", "--routed-probe",
            "--pmc", "none"]
     env = dict(os.environ)
     for k in ("MASTER_PORT", "RANK", "WORLD_SIZE", "LOCAL_RANK"):
