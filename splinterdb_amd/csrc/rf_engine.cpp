@@ -316,7 +316,13 @@ struct rf_amd_batch {
   DevBuf d_plans, d_outs, d_ent, d_part, d_sorted, d_cb_count, d_cb_start, d_cb_cursor, d_cb_filter,
       d_overflow, d_idx_cnt, d_idx_start, d_slots, d_page_first, d_pg_filter, d_pages, d_tile_filter,
       d_tile_start, d_old_tile_filter, d_old_tile_start, d_old_cnt, d_old_pos, d_first_old, d_has_old, d_pplans, d_lines, d_idx_filter, d_spill,
-      d_old_idx_filter, d_old32, d_old_tot, d_ob_lo, d_ob_n, d_pg_noline, d_cb_out;
+      d_old_idx_filter, d_old32, d_old_tot, d_ob_lo, d_ob_n, d_pg_noline, d_cb_out, d_lay_wg, d_lay_hand;
+  // K5 over several workgroups per filter (layout_groups): indices per workgroup, the grid of
+  // k_layout_seg (0: no filter is split), whether any filter keeps one workgroup, and the
+  // sequence number that tags a build's hand-offs (never 0: the words start out zero)
+  uint32_t lay_seg = 0, lay_grid = 0, lay_seq = 0;
+  bool lay_whole = true;
+  bool counters_clean = false;  // the last build ran to its end and left the per-build counters zero (do_build)
   bool built = false;
   bool has_entries = false;  // built here: its sorted entries (d_part / d_sorted) are current
   std::vector<uint32_t> err_host;  // per-filter build error bits once read back (err_ready)
@@ -335,9 +341,21 @@ struct rf_amd_batch {
             &d_cb_filter, &d_overflow, &d_idx_cnt, &d_idx_start, &d_slots, &d_page_first, &d_pg_filter,
             &d_pages, &d_tile_filter, &d_tile_start, &d_old_tile_filter, &d_old_tile_start, &d_old_cnt,
             &d_old_pos, &d_first_old, &d_has_old, &d_pplans, &d_lines, &d_idx_filter, &d_spill,
-            &d_old_idx_filter, &d_old32, &d_old_tot, &d_ob_lo, &d_ob_n, &d_pg_noline, &d_pre, &d_cb_out};
+            &d_old_idx_filter, &d_old32, &d_old_tot, &d_ob_lo, &d_ob_n, &d_pg_noline, &d_pre, &d_cb_out,
+            &d_lay_wg, &d_lay_hand};
   }
 };
+
+// RF_AMD_LAYOUT_SEG: indices per K5 workgroup, a power of two in [256, 4096] (default 4096;
+// larger values mean 4096, 0 or anything else the one-workgroup kernel for every filter).
+// Read when a batch is created.
+static uint32_t layout_seg_env() {
+  const char* e = getenv("RF_AMD_LAYOUT_SEG");
+  if (!e || !*e) return LAYOUT_SEG_MAX;
+  const unsigned long v = strtoul(e, nullptr, 10);
+  if (v < LAYOUT_SEG_MIN || (v & (v - 1))) return 0;
+  return v > LAYOUT_SEG_MAX ? LAYOUT_SEG_MAX : (uint32_t)v;
+}
 
 extern "C" const char* rf_amd_last_error(void) { return g_err.c_str(); }
 
@@ -663,6 +681,29 @@ extern "C" int rf_amd_batch_create(rf_amd_engine* e, const rf_amd_config* cfg, u
       po[f + 1] = po[f] + ((olds[f].second && !p.old_direct) ? p.old_num_indices : 0u);
     }
   }
+  // K5 workgroups: the G segments of a split filter go to one XCD (workgroup w runs on XCD
+  // w % 8), consecutive there, so segment q - 1 is workgroup w - 8: dispatched before its waiter
+  std::vector<uint32_t> lay_wg;
+  b->lay_seg = layout_seg_env();
+  if (P > MAX_PAGE || num_filters >= (1u << 26)) b->lay_seg = 0;
+  {
+    uint32_t pos[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    b->lay_whole = false;
+    for (uint32_t f = 0; f < num_filters; f++) {
+      const uint32_t G = layout_groups(b->plans[f], b->lay_seg);
+      if (G == 1) {
+        b->lay_whole = true;
+        continue;
+      }
+      const uint32_t x = (uint32_t)(std::min_element(pos, pos + 8) - pos);
+      const uint32_t w0 = x + 8 * pos[x];
+      const size_t need = w0 + 8 * (size_t)(G - 1) + 1;
+      if (lay_wg.size() < need) lay_wg.resize(need, ~0u);
+      for (uint32_t q = 0; q < G; q++) lay_wg[w0 + 8 * q] = f << 6 | q;
+      pos[x] += G;
+    }
+    b->lay_grid = (uint32_t)lay_wg.size();
+  }
   b->num_tiles = b->pre_of(rf_amd_batch::PRE_TILE)[num_filters];
   b->num_old_tiles = b->pre_of(rf_amd_batch::PRE_OTILE)[num_filters];
   b->E = e_first;
@@ -692,7 +733,7 @@ extern "C" int rf_amd_batch_create(rf_amd_engine* e, const rf_amd_config* cfg, u
   rc |= b->d_cb_cursor.alloc(4 * b->CB, pool);
   rc |= b->d_cb_filter.alloc(4 * b->CB, pool);
   rc |= b->d_overflow.alloc(4 * (b->CB + 1), pool);
-  rc |= b->d_spill.alloc(4, pool);
+  rc |= b->d_spill.alloc(8, pool);  // the spill flag, the folded K2's ticket
   rc |= b->d_idx_cnt.alloc(4 * b->I, pool);
   rc |= b->d_idx_start.alloc(4 * b->I, pool);
   rc |= b->d_slots.alloc(8 * b->I, pool);
@@ -707,6 +748,10 @@ extern "C" int rf_amd_batch_create(rf_amd_engine* e, const rf_amd_config* cfg, u
   rc |= b->d_old_tile_filter.alloc(4ull * b->num_old_tiles, pool);
   rc |= b->d_old_tile_start.alloc(4ull * b->num_old_tiles, pool);
   rc |= b->d_pre.alloc(4 * b->pre.size(), pool);
+  if (b->lay_grid) {
+    rc |= b->d_lay_wg.alloc(4ull * b->lay_grid, pool);
+    rc |= b->d_lay_hand.alloc(16ull * b->lay_grid, pool);
+  }
   if (b->wide) {
     rc |= b->d_old_cnt.alloc(4ull * b->num_old_idx, pool);
     rc |= b->d_old_pos.alloc(4ull * b->num_old_idx, pool);
@@ -752,7 +797,10 @@ extern "C" int rf_amd_batch_create(rf_amd_engine* e, const rf_amd_config* cfg, u
   }
   UP(b->d_pplans, pp);
   UP(b->d_pre, b->pre);
+  UP(b->d_lay_wg, lay_wg);
 #undef UP
+  // hand-off tags start out zero, once per batch: a build's tag is never 0
+  if (b->lay_grid) HIPCHK(hipMemsetAsync(b->d_lay_hand.p, 0, 16ull * b->lay_grid, st));
   {
     // element -> filter maps (and tile -> first key) from the prefix arrays, on the device
     const uint32_t F1 = num_filters + 1;
@@ -1091,6 +1139,12 @@ static LaunchArgs make_args(rf_amd_batch* b, hipStream_t st) {
   a.num_page_slots = b->PS;
   a.pages = b->d_pages.as<uint8_t>();
   a.outs = b->d_outs.p ? b->d_outs.as<FilterOut>() : nullptr;
+  a.lay_wg = b->d_lay_wg.as<uint32_t>();
+  a.lay_grid = b->d_lay_wg.p && b->d_lay_hand.p ? b->lay_grid : 0;
+  a.lay_hand = b->d_lay_hand.as<uint64_t>();
+  a.lay_seq = b->lay_seq;
+  a.lay_seg = b->lay_seg;
+  a.lay_whole = b->lay_whole ? 1u : 0u;
   a.events = b->events.empty() ? nullptr : reinterpret_cast<void**>(b->events.data() + (size_t)b->ev_set * NUM_EVENTS);
   a.ev_mask = b->ev_mask;
   return a;
@@ -1121,13 +1175,25 @@ static int do_build(rf_amd_batch* b, int kind, const void* in0, const uint64_t* 
   hipStream_t st = stream ? (hipStream_t)stream : b->eng->stream;
   (void)hipGetLastError();  // launch checks below must see only their own errors
   if (b->ev_sets) b->ev_set = (b->ev_set + 1) % b->ev_sets;
+  if (++b->lay_seq == 0) b->lay_seq = 1;
   LaunchArgs a = make_args(b, st);
   a.kind = kind;
   a.in0 = in0;
   a.offs = offs;
   a.key_len = key_len;
   if (a.events && (a.ev_mask >> EV_B_START & 1u)) HIPCHK(hipEventRecord(((hipEvent_t*)a.events)[EV_B_START], st));
-  if (rf_launch_build_init(st, b->d_cb_count.as<uint32_t>(), (b->wide && !b->flag32) ? nullptr : b->d_cb_cursor.as<uint32_t>(),
+  // A fresh build's last kernels leave the per-build counters zero (K5, BuildClean) and its
+  // gated K1 zeroes `outs`, so the init launch runs only for a batch's first build and after
+  // a build whose launches did not all go out. Incremental builds, batches whose probe lines
+  // come from k_plines_list (its page count is read after K5) and the hand-back diagnostics
+  // (read after the build) keep the init launch every time. RF_AMD_SELF_CLEAN=0: always init.
+  const char* sc = getenv("RF_AMD_SELF_CLEAN");
+  a.self_clean = (!b->wide && !b->plines_needed && b->num_tiles && !(sc && sc[0] == '0') &&
+                  !getenv("RF_AMD_DIAG_OVERFLOW")) ? 1u : 0u;
+  a.zero_outs = (a.self_clean && b->counters_clean) ? 1u : 0u;
+  b->counters_clean = false;
+  if (!a.zero_outs &&
+      rf_launch_build_init(st, b->d_cb_count.as<uint32_t>(), (b->wide && !b->flag32) ? nullptr : b->d_cb_cursor.as<uint32_t>(),
                            b->CB, b->d_outs.as<uint32_t>(), (uint32_t)(sizeof(FilterOut) / 4 * b->F),
                            b->d_overflow.as<uint32_t>(), (b->wide && !b->flag32) ? nullptr : b->d_spill.as<uint32_t>(),
                            b->d_pg_noline.as<uint32_t>()))
@@ -1144,6 +1210,7 @@ static int do_build(rf_amd_batch* b, int kind, const void* in0, const uint64_t* 
   // after reading this count cannot miss a build it covers
   if (st == b->eng->stream) b->eng->builds_issued.fetch_add(1, std::memory_order_acq_rel);
   if (rc) return fail(RF_AMD_EINVAL, std::string("build launch: ") + hipGetErrorString((hipError_t)rc));
+  b->counters_clean = a.self_clean != 0;  // every launch of the build went out
   if (getenv("RF_AMD_DIAG_OVERFLOW") && b->d_overflow.p) {  // diagnostics: coarse buckets handed back by K4/K4m
     uint32_t nov = 0;
     if (hipMemcpyAsync(&nov, b->d_overflow.p, 4, hipMemcpyDeviceToHost, st) == hipSuccess &&

@@ -93,6 +93,48 @@ __device__ __forceinline__ uint32_t xcd_chunk(uint32_t b, uint32_t nb) {
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + b / 8;
 }
 
+// K2's body: exclusive scan of one filter's coarse-bucket counts by a 256-thread workgroup
+// (s_tmp: 256/64 + 1 words). counts may alias cb_count / cb_cursor. `fresh`: the counts were
+// added by other workgroups of this kernel (read past this workgroup's caches).
+__device__ __forceinline__ void cb_scan_filter(const FilterPlan& P, const uint32_t* counts, uint32_t* cb_count,
+                                               uint32_t* cb_start, uint32_t* cb_cursor, uint32_t* s_tmp,
+                                               bool fresh) {
+  const uint32_t num_cb = 1u << P.cbits;
+  constexpr uint32_t PER = MAX_CB / 256;
+  uint32_t v[PER], sum = 0;
+#pragma unroll
+  for (uint32_t k = 0; k < PER; k++) {
+    const uint32_t i = threadIdx.x * PER + k;
+    v[k] = 0;
+    if (i < num_cb)
+      v[k] = fresh ? __hip_atomic_load(&counts[P.cb_base + i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+                   : counts[P.cb_base + i];
+    sum += v[k];
+  }
+  uint32_t total;
+  uint32_t run = block_excl_scan<256>(sum, s_tmp, &total);
+#pragma unroll
+  for (uint32_t k = 0; k < PER; k++) {
+    const uint32_t i = threadIdx.x * PER + k;
+    if (i < num_cb) {
+      cb_count[P.cb_base + i] = v[k];
+      cb_start[P.cb_base + i] = run;
+      cb_cursor[P.cb_base + i] = run;
+    }
+    run += v[k];
+  }
+}
+
+// what the gated K1 of a fused build does besides counting ({}: nothing)
+struct CountFold {
+  uint32_t* outs_words;    // the batch's FilterOut words, zeroed here when no init launch ran
+  uint32_t num_out_words;
+  uint32_t* ticket;        // K2 folded in: workgroups that have finished counting
+  uint32_t* cb_count;      // its outputs (the counts themselves become the cursors)
+  uint32_t* cb_start;
+  uint32_t num_filters;
+};
+
 // ======================================================================================
 // K1: hash + coarse-bucket histogram
 // ======================================================================================
@@ -104,9 +146,14 @@ __global__ __launch_bounds__(TILE_NT) void k_hash_count(const FilterPlan* __rest
                                                         const uint64_t* __restrict__ offs,
                                                         uint32_t key_len, uint32_t fp_size,
                                                         uint32_t seed, EntT* __restrict__ ent,
-                                                        uint32_t* __restrict__ cb_count,
-                                                        const uint32_t* __restrict__ gate, uint32_t num_tiles) {
+                                                        uint32_t* cb_count,
+                                                        const uint32_t* __restrict__ gate, uint32_t num_tiles,
+                                                        CountFold fold) {
   __shared__ uint32_t s_hist[MAX_CB];
+  // a build that follows a clean one has no init launch: its outs are zeroed here, before
+  // K4 adds to them (this launch comes before K4 whether or not the partition spilled)
+  if (fold.outs_words && blockIdx.x == 0)
+    for (uint32_t i = threadIdx.x; i < fold.num_out_words; i += TILE_NT) fold.outs_words[i] = 0;
   if (gate && *gate == 0) return;  // fallback pass of the fused build: not needed
   // tiles grid-strided: the gated fallback launches a small grid (it is rarely needed)
   for (uint32_t t = blockIdx.x; t < num_tiles; t += gridDim.x) {
@@ -134,6 +181,21 @@ __global__ __launch_bounds__(TILE_NT) void k_hash_count(const FilterPlan* __rest
     const uint32_t c = s_hist[i];
     if (c) atomicAdd(&cb_count[P.cb_base + i], c);
   }
+  }
+  // K2 folded in (spill fallback only): the last workgroup to finish counting scans every
+  // filter's counts (last-block-done: a ticket after a fence; no workgroup waits for another)
+  if (fold.ticket) {
+    static_assert(TILE_NT == 256, "cb_scan_filter's workgroup");
+    __shared__ uint32_t s_last;
+    __threadfence();
+    __syncthreads();
+    if (threadIdx.x == 0) s_last = atomicAdd(fold.ticket, 1u) == gridDim.x - 1 ? 1u : 0u;
+    __syncthreads();
+    if (!s_last) return;
+    __threadfence();
+    if (threadIdx.x == 0) *fold.ticket = 0;  // for the next spilled build
+    for (uint32_t f = 0; f < fold.num_filters; f++)
+      cb_scan_filter(plans[f], cb_count, fold.cb_count, fold.cb_start, cb_count, s_hist, true);
   }
 }
 
@@ -177,28 +239,7 @@ __global__ __launch_bounds__(256) void k_cb_scan(const FilterPlan* __restrict__ 
                                                  const uint32_t* __restrict__ gate) {
   __shared__ uint32_t s_tmp[256 / WAVE + 1];
   if (gate && *gate == 0) return;
-  const FilterPlan& P = plans[blockIdx.x];
-  const uint32_t num_cb = 1u << P.cbits;
-  constexpr uint32_t PER = MAX_CB / 256;
-  uint32_t v[PER], sum = 0;
-#pragma unroll
-  for (uint32_t k = 0; k < PER; k++) {
-    const uint32_t i = threadIdx.x * PER + k;
-    v[k] = i < num_cb ? counts[P.cb_base + i] : 0u;
-    sum += v[k];
-  }
-  uint32_t total;
-  uint32_t run = block_excl_scan<256>(sum, s_tmp, &total);
-#pragma unroll
-  for (uint32_t k = 0; k < PER; k++) {
-    const uint32_t i = threadIdx.x * PER + k;
-    if (i < num_cb) {
-      cb_count[P.cb_base + i] = v[k];
-      cb_start[P.cb_base + i] = run;
-      cb_cursor[P.cb_base + i] = run;
-    }
-    run += v[k];
-  }
+  cb_scan_filter(plans[blockIdx.x], counts, cb_count, cb_start, cb_cursor, s_tmp, false);
 }
 
 // ======================================================================================
@@ -1501,6 +1542,30 @@ __device__ __forceinline__ uint32_t block_size(uint32_t c, uint32_t index_size, 
   return enc + 2 + rbs;
 }
 
+// The per-build counters (coarse-bucket counts and cursors, K4's hand-back count, the spill
+// flag) are last read by K4 / K4b, so K5's workgroups leave them zero for the batch's next
+// build, which then needs no init launch. cb_count == nullptr: not this build.
+struct BuildClean {
+  uint32_t* cb_count;
+  uint32_t* cb_cursor;
+  uint32_t* overflow;
+  uint32_t* spill;
+};
+// workgroup q of the G that lay out filter f
+__device__ __forceinline__ void clean_counters(const BuildClean& c, const FilterPlan& P, uint32_t f, uint32_t q,
+                                               uint32_t G) {
+  if (!c.cb_count) return;
+  const uint32_t ncb = 1u << P.cbits;
+  for (uint32_t i = q * LAYOUT_NT + threadIdx.x; i < ncb; i += G * LAYOUT_NT) {
+    c.cb_count[P.cb_base + i] = 0;
+    c.cb_cursor[P.cb_base + i] = 0;
+  }
+  if (f == 0 && q == 0 && threadIdx.x == 0) {
+    c.overflow[0] = 0;
+    c.spill[0] = 0;
+  }
+}
+
 constexpr uint32_t LAYOUT_LIST = 520;
 __global__ __launch_bounds__(LAYOUT_NT) void k_layout(const FilterPlan* __restrict__ plans,
                                                       const uint32_t* __restrict__ idx_cnt,
@@ -1512,7 +1577,8 @@ __global__ __launch_bounds__(LAYOUT_NT) void k_layout(const FilterPlan* __restri
                                                       uint64_t* __restrict__ slots,
                                                       uint32_t* __restrict__ page_first,
                                                       FilterOut* __restrict__ outs,
-                                                      uint32_t lis, uint32_t page_size) {
+                                                      uint32_t lis, uint32_t page_size, uint32_t seg,
+                                                      BuildClean clean) {
   __shared__ uint32_t s_excl[MAX_INDICES + 1];
   __shared__ uint16_t s_jA[MAX_INDICES + 1];
   __shared__ uint16_t s_jB[MAX_INDICES + 1];
@@ -1527,6 +1593,8 @@ __global__ __launch_bounds__(LAYOUT_NT) void k_layout(const FilterPlan* __restri
   const uint32_t n = P.num_indices;
   const uint32_t index_size = 1u << lis;
   constexpr int PER = MAX_INDICES / LAYOUT_NT;
+  if (layout_groups(P, seg) > 1) return;  // laid out by k_layout_seg's workgroups
+  clean_counters(clean, P, f, 0, 1);      // before any return below
   DBG_PHASE_K(4, 15);
   if (threadIdx.x == 0) s_err = 0;
   __syncthreads();
@@ -1749,6 +1817,380 @@ __global__ __launch_bounds__(LAYOUT_NT) void k_layout(const FilterPlan* __restri
     if (npages > P.page_cap) {
       outs[f].error |= ERR_PAGE_CAP;
       pplans[f].w = ERR_PAGE_CAP;
+    }
+  }
+  DBG_PHASE_K(4, 8);
+}
+
+// --------------------------------------------------------------------------------------
+// K5 over G = num_indices / seg workgroups per filter (layout_groups). Segment q owns the
+// indices [q seg, (q + 1) seg) and loads a halo of the sizes after them, as many blocks as
+// one page can hold, so next() of its own blocks never needs another workgroup. Which of
+// its blocks start pages depends on one number from the segments before it, the first page
+// start at or after its first index (its entry). The entry can only be one of the first
+// halo + 1 blocks, so before it knows the entry the segment tabulates, for each of them, the
+// exit (first page start past the segment), the page starts on the way and the bytes of the
+// page left open at the segment's end. When the hand-off of segment q - 1 arrives, one table
+// lookup gives the hand-off for q + 1, published before the marks, page numbers and slots.
+//
+// Hand-off of workgroup b, two 64-bit words at hand[2 b]: {entry << 32 | pages before the
+// entry}, then {tag << 32 | failed << 31 | bytes of the open page before the next segment}.
+// The second word is stored with release, polled with acquire (agent scope: the filter's
+// workgroups are placed on one XCD, but nothing relies on that); it is valid when its tag is
+// this build's sequence number, so the words are never cleared. A workgroup's predecessor is
+// b - 8: a lower id, dispatched first, so a waiter never keeps its predecessor off the GPU.
+// Every return publishes, and the wait gives up after LSEG_POLLS polls (about a second):
+// the filter is then reported failed (ERR_PAGE_CAP) and the successor told so.
+// --------------------------------------------------------------------------------------
+constexpr uint32_t LSEG_PERC = 5;                                 // contiguous elements per thread of the size scan
+constexpr uint32_t LSEG_W = LAYOUT_NT * LSEG_PERC;                // >= seg + halo
+constexpr uint32_t LSEG_HALO = MAX_PAGE / 9 + 1;                  // smallest block: 9 bytes (lis 3, no entries)
+constexpr uint32_t LSEG_LIST = 160;                               // every 2^R-th page start of a segment (<= ~70)
+constexpr uint32_t LSEG_POLLS = 1u << 20;
+constexpr uint32_t LSEG_FAIL = 1u << 31;
+static_assert(LAYOUT_SEG_MAX + LSEG_HALO + 1 <= LSEG_W, "segment + halo fit the size scan");
+static_assert(LAYOUT_SEG_MAX == 4 * LAYOUT_NT, "four own blocks per thread");
+
+__device__ __forceinline__ void lseg_publish(uint64_t* hand, uint32_t b, uint32_t seq, uint32_t entry,
+                                             uint32_t pages, uint32_t open_or_fail) {
+  __hip_atomic_store(&hand[2 * b], (uint64_t)entry << 32 | pages, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __hip_atomic_store(&hand[2 * b + 1], (uint64_t)seq << 32 | open_or_fail, __ATOMIC_RELEASE,
+                     __HIP_MEMORY_SCOPE_AGENT);
+}
+// one thread: the hand-off of workgroup b; false if it failed or did not come in time
+__device__ __forceinline__ bool lseg_wait(const uint64_t* hand, uint32_t b, uint32_t seq, uint32_t* entry,
+                                          uint32_t* pages, uint32_t* open, bool* timed_out) {
+  *timed_out = false;
+  for (uint32_t poll = 0; poll < LSEG_POLLS; poll++) {
+    const uint64_t w1 = __hip_atomic_load(&hand[2 * b + 1], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
+    if ((uint32_t)(w1 >> 32) == seq) {
+      const uint64_t w0 = __hip_atomic_load(&hand[2 * b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      *entry = (uint32_t)(w0 >> 32);
+      *pages = (uint32_t)w0;
+      *open = (uint32_t)w1 & ~LSEG_FAIL;
+      return !((uint32_t)w1 & LSEG_FAIL);
+    }
+    __builtin_amdgcn_s_sleep(8);
+  }
+  *timed_out = true;
+  return false;
+}
+
+__global__ __launch_bounds__(LAYOUT_NT) void k_layout_seg(const FilterPlan* __restrict__ plans,
+                                                          const uint32_t* __restrict__ lay_wg,
+                                                          uint64_t* hand, uint32_t seq, uint32_t seg,
+                                                          const uint32_t* __restrict__ idx_cnt,
+                                                          const uint32_t* __restrict__ idx_start,
+                                                          const uint32_t* __restrict__ sorted32,
+                                                          const uint32_t* __restrict__ first_old,
+                                                          const uint32_t* __restrict__ has_old,
+                                                          uint4* __restrict__ pplans,
+                                                          uint64_t* __restrict__ slots,
+                                                          uint32_t* __restrict__ page_first,
+                                                          FilterOut* __restrict__ outs,
+                                                          uint32_t lis, uint32_t page_size, BuildClean clean) {
+  __shared__ uint32_t s_excl[LSEG_W + 1];   // sizes, then their exclusive prefix (local: [0] = 0)
+  __shared__ uint32_t s_T[LSEG_W + 1];      // page starts passed << 16 | next^(2^R), absorbing at >= seg
+  __shared__ uint16_t s_jA[LSEG_W + 1];     // next()
+  __shared__ uint32_t s_mark32[LAYOUT_SEG_MAX / 4];
+  __shared__ uint16_t s_pstart[LAYOUT_SEG_MAX + 1];  // local page -> its first block
+  __shared__ uint16_t s_list[LSEG_LIST];
+  __shared__ uint32_t s_hexit[LSEG_HALO + 2], s_hcnt[LSEG_HALO + 2], s_hopen[LSEG_HALO + 2];  // per entry
+  __shared__ uint32_t s_tmp[LAYOUT_NT / WAVE + 1];
+  __shared__ uint32_t s_err, s_nlist, s_in[4];
+  const uint32_t b = blockIdx.x;
+  const uint32_t wg = lay_wg[b];
+  if (wg == ~0u) return;
+  const uint32_t f = wg >> 6, q = wg & 63u;
+  const FilterPlan& P = plans[f];
+  const uint32_t n = P.num_indices;
+  const uint32_t G = n / seg, base = q * seg;
+  const bool last = q + 1 == G;
+  clean_counters(clean, P, f, q, G);  // before any return below
+  const uint32_t index_size = 1u << lis;
+  const uint32_t hmax = min(page_size / ((index_size - 1) / 8 + 9) + 1, LSEG_HALO);  // blocks a page can hold, + 1
+  const uint32_t H = min(n - base - seg, hmax);
+  const uint32_t L = seg + H;  // blocks in the window; the last segment's ends at n
+  uint8_t* s_mark = reinterpret_cast<uint8_t*>(s_mark32);
+  DBG_PHASE_K(4, 15);
+  if (threadIdx.x == 0) s_err = 0;
+  for (uint32_t i = threadIdx.x; i < LAYOUT_SEG_MAX / 4; i += LAYOUT_NT) s_mark32[i] = 0;
+  // sizes (k-major: coalesced loads, every load before the first use), then one scan over
+  // each thread's LSEG_PERC consecutive elements
+  uint32_t sz[LSEG_PERC], err = 0;
+#pragma unroll
+  for (uint32_t k = 0; k < LSEG_PERC; k++)
+    sz[k] = idx_cnt[P.idx_base + base + min(k * LAYOUT_NT + threadIdx.x, L - 1)];
+#pragma unroll
+  for (uint32_t k = 0; k < LSEG_PERC; k++) {
+    const uint32_t i = k * LAYOUT_NT + threadIdx.x;
+    const uint32_t c = sz[k];
+    const uint32_t s = block_size(c, index_size, P.rvs);
+    if (i < seg) {  // the halo's blocks are checked by their own segment
+      if (c > 4096) err |= ERR_INDEX_OVERFLOW;
+      if (s > page_size) err |= ERR_BLOCK_TOO_BIG;
+    }
+    s_excl[i] = i < L ? s : 0u;
+  }
+  __syncthreads();
+  if (err) atomicOr(&s_err, err);
+  DBG_PHASE_K(4, 5);
+  {
+    uint32_t v[LSEG_PERC], sum = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < LSEG_PERC; k++) {
+      v[k] = s_excl[threadIdx.x * LSEG_PERC + k];
+      sum += v[k];
+    }
+    uint32_t total;
+    uint32_t e = block_excl_scan<LAYOUT_NT>(sum, s_tmp, &total);  // barriers: s_err is settled after it
+#pragma unroll
+    for (uint32_t k = 0; k < LSEG_PERC; k++) {  // only this thread read these words
+      s_excl[threadIdx.x * LSEG_PERC + k] = e;  // [L] (< LSEG_W) becomes the window's total
+      e += v[k];
+    }
+  }
+  __syncthreads();
+  DBG_PHASE_K(4, 6);
+  const uint32_t pred = b - 8;  // segment q - 1 (q > 0)
+  if (s_err) {
+    // publish first, so that no successor waits for this return. pplans[f].w (probes of a
+    // failed filter find nothing: only tested for nonzero) is cleared by segment 0 before it
+    // publishes; the first failing segment's OR comes after its wait, so after that clear.
+    if (threadIdx.x == 0) {
+      if (q == 0) pplans[f].w = 0;
+      if (!last) lseg_publish(hand, b, seq, 0, 0, LSEG_FAIL);
+      atomicOr(&outs[f].error, s_err);
+      uint32_t e0, p0, o0;
+      bool late = false;
+      if (q) (void)lseg_wait(hand, pred, seq, &e0, &p0, &o0, &late);
+      atomicOr(&pplans[f].w, s_err | (late ? ERR_PAGE_CAP : 0u));
+      if (late) atomicOr(&outs[f].error, ERR_PAGE_CAP);
+    }
+    return;
+  }
+  DBG_PHASE_K(4, 0);
+  // next() of the own blocks, as in k_layout: runs of consecutive blocks, gallop + bisect for
+  // the first, then the pointer only advances. L stands for "none" (only when the window ends at n).
+  {
+    const uint32_t run = ((seg + LAYOUT_NT - 1) / LAYOUT_NT) | 1u;
+    const uint32_t j0 = threadIdx.x * run, j1 = min(j0 + run, seg);
+    uint32_t qp = 0;
+#pragma unroll 1
+    for (uint32_t j = j0; j < j1; j++) {
+      const uint32_t lim = s_excl[j] + page_size;
+      if (j == j0) {
+        qp = j + 1;
+        if (qp <= L && s_excl[qp] <= lim) {
+          uint32_t lo = qp, hi = qp + 1, step = 1;  // excl[lo] <= lim
+          while (hi <= L && s_excl[hi] <= lim) {
+            lo = hi;
+            step <<= 1;
+            hi = lo + step;
+          }
+          if (hi > L + 1) hi = L + 1;
+          while (hi - lo > 1) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (s_excl[mid] <= lim) lo = mid; else hi = mid;
+          }
+          qp = hi;
+        }
+      } else {
+        qp = max(qp, j + 1);
+        while (qp <= L && s_excl[qp] <= lim) qp++;
+      }
+      s_jA[j] = (uint16_t)(qp - 1);  // in (j, L]: every block fits a page
+      s_T[j] = 1u << 16 | (qp - 1);
+    }
+    for (uint32_t j = seg + threadIdx.x; j <= L; j += LAYOUT_NT) {  // past the segment: fixed points
+      s_jA[j] = (uint16_t)j;
+      s_T[j] = j;
+    }
+  }
+  __syncthreads();
+  DBG_PHASE_K(4, 1);
+  // R rounds of pointer doubling that also add up the page starts passed
+  const uint32_t est = s_excl[seg] / page_size + 1;  // the segment's pages: >= est - 1, <= 2 est + 1
+  const uint32_t lg = 32u - __clz(est);
+  const uint32_t R = min(8u, lg > 5 ? lg - 5 : 1u);
+  for (uint32_t r = 0; r < R; r++) {
+    uint32_t c1[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      const uint32_t j = threadIdx.x + k * LAYOUT_NT;
+      c1[k] = j < seg ? s_T[j] : 0u;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      const uint32_t j = threadIdx.x + k * LAYOUT_NT;
+      if (j < seg) {
+        const uint32_t w = s_T[c1[k] & 0xffffu];
+        c1[k] = ((c1[k] & 0xffff0000u) + (w & 0xffff0000u)) | (w & 0xffffu);
+      }
+    }
+    __syncthreads();  // every read of this round before any write
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      const uint32_t j = threadIdx.x + k * LAYOUT_NT;
+      if (j < seg) s_T[j] = c1[k];
+    }
+    __syncthreads();
+  }
+  // the table: entry e -> exit, page starts in the segment, bytes of the page open at its end
+  if (threadIdx.x <= hmax && threadIdx.x < seg) {
+    uint32_t x = threadIdx.x, c = 0, y = x;
+    while (x < seg) {  // next() only goes forward: at most seg steps
+      y = x;
+      const uint32_t v = s_T[x];
+      c += v >> 16;
+      x = v & 0xffffu;
+    }
+    for (;;) {  // the last page start before the exit
+      const uint32_t z = s_jA[y];
+      if (z >= seg) break;
+      y = z;
+    }
+    s_hexit[threadIdx.x] = x;
+    s_hcnt[threadIdx.x] = c;
+    s_hopen[threadIdx.x] = s_excl[seg] - s_excl[y];
+  }
+  __syncthreads();
+  DBG_PHASE_K(4, 2);
+  // stitch: take the entry from segment q - 1, hand the exit to segment q + 1
+  if (threadIdx.x == 0) {
+    uint32_t entry = 0, pages = 0, open = 0, bad = 0;
+    if (q) {
+      bool late;
+      if (!lseg_wait(hand, pred, seq, &entry, &pages, &open, &late)) bad = late ? ERR_PAGE_CAP : LSEG_FAIL;
+      // an entry is at most a halo past the predecessor's end (never trust a word from memory as an index)
+      else if (entry < base || entry - base > hmax || entry > n) bad = ERR_PAGE_CAP;
+    }
+    uint32_t el = entry - base, ex = 0, cnt = 0, op = 0;
+    if (!bad) {
+      if (el >= seg) {  // no page starts in this segment
+        ex = entry;
+        op = open + s_excl[seg];
+      } else {
+        ex = base + s_hexit[el];
+        cnt = s_hcnt[el];
+        op = s_hopen[el];
+      }
+    }
+    if (q == 0) pplans[f].w = 0;  // before the release below: later segments' ORs come after it
+    if (!last) lseg_publish(hand, b, seq, ex, pages + cnt, bad ? LSEG_FAIL : op);
+    if (!bad) {
+      // coarse page starts from the entry (every 2^R-th), for the marks below
+      uint32_t m = 0, x = el;
+      while (x < seg && m < LSEG_LIST) {
+        s_list[m++] = (uint16_t)x;
+        x = s_T[x] & 0xffffu;
+      }
+      s_nlist = m;
+      if (x < seg) bad = ERR_PAGE_CAP;  // cannot happen (m <= ~70); reported, never silently wrong
+    }
+    if (bad & ~LSEG_FAIL) {
+      atomicOr(&outs[f].error, bad);
+      atomicOr(&pplans[f].w, bad);
+    }
+    s_in[0] = el;
+    s_in[1] = pages;
+    s_in[2] = open;
+    s_in[3] = bad;
+  }
+  __syncthreads();
+  if (s_in[3]) return;
+  const uint32_t pbefore = s_in[1], dopen = s_in[2];
+  DBG_PHASE_K(4, 7);
+  {
+    const uint32_t m = s_nlist;
+    for (uint32_t i = threadIdx.x; i < m; i += LAYOUT_NT) {
+      uint32_t x = s_list[i];
+      s_mark[x] = 1;
+      for (uint32_t st = 1; st < (1u << R); st++) {
+        x = s_jA[x];
+        if (x >= seg) break;
+        s_mark[x] = 1;
+      }
+    }
+  }
+  __syncthreads();
+  // page numbers and slots: thread t owns blocks 4 t .. 4 t + 3
+  const uint32_t mk4 = threadIdx.x * 4 < seg ? s_mark32[threadIdx.x] : 0u;
+  uint32_t npl;
+  uint32_t lp = block_excl_scan<LAYOUT_NT>(__popc(mk4), s_tmp, &npl);  // local page starts before 4 t
+#pragma unroll
+  for (uint32_t k = 0; k < 4; k++)
+    if (mk4 >> (8 * k) & 1u) s_pstart[lp + __popc(mk4 & ((1u << (8 * k)) - 1u))] = (uint16_t)(threadIdx.x * 4 + k);
+  __syncthreads();
+  uint32_t* pf = page_first + P.pf_base;
+  if (threadIdx.x * 4 < seg) {
+#pragma unroll
+    for (uint32_t k = 0; k < 4; k++) {
+      const uint32_t j = threadIdx.x * 4 + k;
+      const uint32_t isst = mk4 >> (8 * k) & 1u;
+      const uint32_t inc = lp + __popc(mk4 & ((2u << (8 * k)) - 1u));  // local page starts up to and with j
+      uint32_t page, off;
+      if (inc == 0) {  // still on the page opened before this segment
+        page = pbefore - 1;
+        off = dopen + s_excl[j];
+      } else {
+        page = pbefore + inc - 1;
+        off = s_excl[j] - s_excl[s_pstart[inc - 1]];
+      }
+      slots[P.idx_base + base + j] = (uint64_t)page * page_size + off;
+      if (isst && page < P.page_cap) pf[page] = base + j;
+    }
+  }
+  DBG_PHASE_K(4, 3);
+  // num_unique quirk of the old/new merge, as in k_layout; its groups of npo indices lie
+  // inside the segment (layout_groups)
+  if (P.npo > 1) {
+    uint32_t loc[4], m = 0xffffffffu;
+#pragma unroll
+    for (int k = 3; k >= 0; k--) {
+      const uint32_t j = threadIdx.x * 4 + k;
+      loc[k] = m;
+      if (j < seg && has_old[P.idx_base + base + j]) m = base + j;
+    }
+    uint32_t x = m;
+    const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
+#pragma unroll
+    for (int d = 1; d < WAVE; d <<= 1) {
+      const uint32_t y = __shfl_down(x, d, WAVE);
+      if (lane + d < WAVE) x = min(x, y);
+    }
+    __syncthreads();  // block_excl_scan above has read s_tmp
+    if (lane == 0) s_tmp[wv] = x;
+    __syncthreads();
+    uint32_t after_wave = 0xffffffffu;
+    for (int w2 = wv + 1; w2 < LAYOUT_NT / WAVE; w2++) after_wave = min(after_wave, s_tmp[w2]);
+    __syncthreads();
+    uint32_t xn = __shfl_down(x, 1, WAVE);
+    if (lane == WAVE - 1) xn = 0xffffffffu;
+    const uint32_t beyond = min(xn, after_wave);
+    uint32_t extra = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      const uint32_t jl = threadIdx.x * 4 + k, j = base + jl;
+      const uint32_t nx = min(loc[k], beyond);
+      if (jl < seg && (j + 1) % P.npo != 0 && nx < (j / P.npo + 1) * P.npo) {
+        const uint32_t c = idx_cnt[P.idx_base + j];
+        const uint32_t lastv = c ? sorted32[P.e_first + idx_start[P.idx_base + j] + c - 1] : 0xffffffffu;
+        const uint32_t peek = first_old[P.idx_base + nx];
+        if ((peek >> P.vs) != (lastv >> P.vs)) extra++;
+      }
+    }
+    uint32_t tot_extra;
+    block_excl_scan<LAYOUT_NT>(extra, s_tmp, &tot_extra);
+    if (threadIdx.x == 0 && tot_extra) atomicAdd(&outs[f].num_unique, tot_extra);
+  }
+  if (last && threadIdx.x == 0) {
+    const uint32_t npages = pbefore + npl;
+    if (npages <= P.page_cap) pf[npages] = n;
+    outs[f].num_pages = npages;
+    if (npages > P.page_cap) {
+      atomicOr(&outs[f].error, ERR_PAGE_CAP);
+      atomicOr(&pplans[f].w, ERR_PAGE_CAP);
     }
   }
   DBG_PHASE_K(4, 8);
@@ -2521,7 +2963,7 @@ __global__ __launch_bounds__(256) void k_build_init(uint32_t* __restrict__ cb_co
   for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < num_out_words; i += stride) outs_words[i] = 0;
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     overflow[0] = 0;
-    if (spill) spill[0] = 0;
+    if (spill) spill[0] = spill[1] = 0;  // the flag, and the folded K2's ticket (k_hash_count)
     if (plist) plist[0] = 0;  // k_plines_list's page count
   }
 }
@@ -3974,10 +4416,11 @@ extern "C" int rf_launch_probe_groups(void* stream, const uint32_t* in, const Pr
 constexpr uint32_t GATED_GRID = 256;
 
 template <typename EntT, bool FL = (sizeof(EntT) == 8)>
-static int launch_hash_count_t(const LaunchArgs& a, EntT* ent, uint32_t* counts, const uint32_t* gate) {
+static int launch_hash_count_t(const LaunchArgs& a, EntT* ent, uint32_t* counts, const uint32_t* gate,
+                               const CountFold& fold) {
   dim3 g(gate ? min(a.num_tiles, GATED_GRID) : a.num_tiles), b(TILE_NT);
 #define L(K) hipLaunchKernelGGL((k_hash_count<K, EntT, FL>), g, b, 0, (hipStream_t)a.stream, a.plans, a.tile_filter, \
-                                a.tile_start, a.in0, a.offs, a.key_len, a.fp_size, a.seed, ent, counts, gate, a.num_tiles)
+                                a.tile_start, a.in0, a.offs, a.key_len, a.fp_size, a.seed, ent, counts, gate, a.num_tiles, fold)
   KIND_SWITCH(a.kind, L);
 #undef L
   CHECK_LAUNCH();
@@ -4068,11 +4511,12 @@ extern "C" int rf_launch_build(const LaunchArgs* pa) {
 #undef L
       CHECK_LAUNCH();
     }
-    // spill fallback (returns at once unless *spill): exact new counts, packed starts, scatter
-    if (a.num_tiles) { int rc = launch_hash_count_t<uint32_t, true>(a, ent, a.cb_cursor, a.spill); if (rc) return rc; }
-    hipLaunchKernelGGL(k_cb_scan, dim3(a.num_filters), dim3(256), 0, (hipStream_t)a.stream, a.plans, a.cb_cursor,
-                       a.cb_count, a.cb_start, a.cb_cursor, a.spill);
-    CHECK_LAUNCH();
+    // spill fallback (returns at once unless *spill): exact new counts and, by the last
+    // workgroup to finish them, the packed starts (K2 folded into K1); scatter
+    if (a.num_tiles) {
+      const CountFold fold{nullptr, 0, a.spill + 1, a.cb_count, a.cb_start, a.num_filters};
+      if (int rc = launch_hash_count_t<uint32_t, true>(a, ent, a.cb_cursor, a.spill, fold)) return rc;
+    }
     if (int rc = launch_scatter_t<uint32_t, true>(a, ent, part, a.spill)) return rc;
     if (a.num_cb) {
       hipLaunchKernelGGL(k_old_cb_bounds, dim3((a.num_cb + 255) / 256), dim3(256), 0, (hipStream_t)a.stream, a.plans,
@@ -4096,7 +4540,7 @@ extern "C" int rf_launch_build(const LaunchArgs* pa) {
                          a.old_tile_filter, a.old_tile_start, a.fp_size, ent, a.cb_count);
       CHECK_LAUNCH();
     }
-    if (a.num_tiles) { int rc = launch_hash_count_t<uint64_t>(a, ent, a.cb_count, nullptr); if (rc) return rc; }
+    if (a.num_tiles) { int rc = launch_hash_count_t<uint64_t>(a, ent, a.cb_count, nullptr, CountFold{}); if (rc) return rc; }
     REC(EV_B_HASH);
     hipLaunchKernelGGL(k_cb_scan, dim3(a.num_filters), dim3(256), 0, (hipStream_t)a.stream, a.plans, a.cb_count,
                        a.cb_count, a.cb_start, a.cb_cursor, nullptr);
@@ -4118,20 +4562,36 @@ extern "C" int rf_launch_build(const LaunchArgs* pa) {
       CHECK_LAUNCH();
     }
     REC(EV_B_HASH);
-    // spill fallback (every kernel returns at once unless *spill): exact counts into
-    // cb_cursor, scan -> cb_count / cb_start / cb_cursor, scatter from the entry array
-    if (a.num_tiles) { int rc = launch_hash_count_t<uint32_t>(a, ent, a.cb_cursor, a.spill); if (rc) return rc; }
-    hipLaunchKernelGGL(k_cb_scan, dim3(a.num_filters), dim3(256), 0, (hipStream_t)a.stream, a.plans, a.cb_cursor,
-                       a.cb_count, a.cb_start, a.cb_cursor, a.spill);
-    CHECK_LAUNCH();
+    // spill fallback (both kernels return at once unless *spill): exact counts into cb_cursor
+    // and, by the last workgroup to finish them, their scan -> cb_count / cb_start / cb_cursor
+    // (K2 folded into K1); scatter from the entry array. The first of them also zeroes the
+    // filters' outs when no init launch did (a.zero_outs).
+    if (a.num_tiles) {
+      const CountFold fold{a.zero_outs ? (uint32_t*)a.outs : nullptr, (uint32_t)(sizeof(FilterOut) / 4) * a.num_filters,
+                           a.spill + 1, a.cb_count, a.cb_start, a.num_filters};
+      if (int rc = launch_hash_count_t<uint32_t>(a, ent, a.cb_cursor, a.spill, fold)) return rc;
+    }
     REC(EV_B_SCAN);
     if (int rc = launch_scatter_t<uint32_t>(a, ent, part, a.spill)) return rc;
     REC(EV_B_SCATTER);
     if (int rc = launch_sort_t<uint32_t>(a, ent, part, a.spill)) return rc;
   }
-  hipLaunchKernelGGL(k_layout, dim3(a.num_filters), dim3(LAYOUT_NT), 0, (hipStream_t)a.stream, a.plans, a.idx_cnt,
-                     a.idx_start, a.sorted32, a.first_old, a.has_old, a.pplans_mut, a.slots, a.page_first, a.outs, a.lis, a.page_size);
-  CHECK_LAUNCH();
+  // the build's counters left zero for the next build (a.self_clean: fresh builds)
+  const BuildClean clean = a.self_clean ? BuildClean{a.cb_count, a.cb_cursor, a.overflow, a.spill}
+                                        : BuildClean{nullptr, nullptr, nullptr, nullptr};
+  // K5: one launch unless the batch mixes filters of more than lay_seg indices with smaller ones
+  if (a.lay_whole || !a.lay_grid) {
+    hipLaunchKernelGGL(k_layout, dim3(a.num_filters), dim3(LAYOUT_NT), 0, (hipStream_t)a.stream, a.plans, a.idx_cnt,
+                       a.idx_start, a.sorted32, a.first_old, a.has_old, a.pplans_mut, a.slots, a.page_first, a.outs,
+                       a.lis, a.page_size, a.lay_grid ? a.lay_seg : 0u, clean);
+    CHECK_LAUNCH();
+  }
+  if (a.lay_grid) {
+    hipLaunchKernelGGL(k_layout_seg, dim3(a.lay_grid), dim3(LAYOUT_NT), 0, (hipStream_t)a.stream, a.plans, a.lay_wg,
+                       a.lay_hand, a.lay_seq, a.lay_seg, a.idx_cnt, a.idx_start, a.sorted32, a.first_old, a.has_old,
+                       a.pplans_mut, a.slots, a.page_first, a.outs, a.lis, a.page_size, clean);
+    CHECK_LAUNCH();
+  }
   REC(EV_B_LAYOUT);
   hipLaunchKernelGGL(k_assemble, dim3(a.num_page_slots), dim3(ASM_NT), 0, (hipStream_t)a.stream, a.plans, a.pg_filter,
                      a.idx_cnt, a.idx_start, a.sorted32, a.slots, a.page_first, a.outs, a.pages, a.lines,

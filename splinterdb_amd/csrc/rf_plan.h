@@ -78,6 +78,15 @@ struct FilterPlan {
   const uint32_t* old_idx_cnt;
 };
 
+// K5 (page layout) workgroups of a filter: `seg` indices each when the filter has more than
+// that. seg is a power of two in [256, LAYOUT_SEG_MAX] or 0 (never split); the put-back
+// quirk's groups of npo indices must not straddle a segment.
+constexpr uint32_t LAYOUT_SEG_MAX = 4096, LAYOUT_SEG_MIN = 256;
+constexpr uint32_t LAYOUT_MAX_GROUPS = MAX_INDICES / LAYOUT_SEG_MIN;  // 64: 6 bits of a lay_wg word
+__host__ __device__ inline uint32_t layout_groups(const FilterPlan& p, uint32_t seg) {
+  return (seg && p.num_indices > seg && p.npo <= seg) ? p.num_indices / seg : 1u;
+}
+
 // one filter of routing_filter_estimate_unique_fp (src/routing_filter.c:702-848): the first
 // num_indices/16 indices of its image are decoded into a fingerprint bitmap
 struct EstFilter {
@@ -213,6 +222,16 @@ struct LaunchArgs {
   uint32_t num_page_slots;
   uint8_t* pages;
   FilterOut* outs;
+  // K5 over several workgroups per filter (layout_groups): workgroup -> filter << 6 | segment
+  // (~0: none), the hand-off words (2 per workgroup), this build's hand-off tag
+  const uint32_t* lay_wg;
+  uint32_t lay_grid;
+  uint64_t* lay_hand;
+  uint32_t lay_seq;
+  uint32_t lay_seg;    // indices per layout workgroup (0: one workgroup per filter)
+  uint32_t lay_whole;  // some filter of the batch is laid out by one workgroup
+  uint32_t self_clean;  // K5 leaves the build's counters zero: the next build skips k_build_init
+  uint32_t zero_outs;   // no k_build_init ran before this build: it zeroes `outs` itself
   const uint64_t* probe_runs;  // probes grouped by filter: runs[f] <= i < runs[f+1] (nullptr: per-probe ids)
   const uint32_t* wave_tab;    // with probe_runs: per 64-probe wave, filter << 7 | leading probes in it
   void** events;  // optional hipEvent_t[NUM_EVENTS] for per-stage timing (nullptr = off)

@@ -47,6 +47,7 @@ else:
 E._check(L.rf_amd_debug_phase_buffer(None, 0))
 ts = buf.cpu().numpy().reshape(-1, 16)
 used = ts[:, 8] != 0
+wg_id = np.nonzero(used)[0]
 ts = ts[used]
 print(f"workgroups stamped: {ts.shape[0]}")
 if KID == 1:
@@ -62,6 +63,15 @@ elif KID == 4:
     names = {15: "entry", 5: "size loads (t0)", 6: "scan", 0: "excl store", 1: "next()", 2: "doubling",
              3: "pages+slots", 8: "quirk+end"}
     order = [15, 5, 6, 0, 1, 2, 3, 8]
+    if (ts[:, 7] != 0).all():  # k_layout_seg: workgroup w is segment w // 8 of its filter's chain
+        names.update({2: "doubling+table", 7: "stitch (wait)", 3: "marks+pages+slots"})
+        order = [15, 5, 6, 0, 1, 2, 7, 3, 8]
+        # (only differences within a workgroup: the stamps of different workgroups, even of one
+        # chain, are millions of cycles apart -- profiles/r07_phase_layout.txt's last column)
+        for q in sorted(set(wg_id // 8)):
+            r = ts[wg_id // 8 == q]
+            print(f"segment {q}: " + "  ".join(f"{names[c]} {(r[:, c] - r[:, a]).mean():.0f}"
+                                             for a, c in zip(order[:-1], order[1:])))
 elif KID == 3:
     names = {15: "entry", 0: "metadata", 1: "fill", 2: "entry runs", 3: "store", 4: "line scan",
              8: "line write"}
