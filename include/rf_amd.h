@@ -74,6 +74,26 @@ int rf_amd_batch_create(rf_amd_engine *e, const rf_amd_config *cfg, uint32_t num
                         const uint32_t *num_new, const uint16_t *value,
                         rf_amd_batch *const *old_batch, const uint32_t *old_index,
                         rf_amd_batch **out);
+/* A chained batch: filter f is the end of a chain of num_runs[f] routing_filter_add calls
+ * (maplet_compaction_task's loop over a pivot's bundle compactions, src/trunk.c:3815-3868,
+ * which keeps only the last filter), built in one build. Run j of filter f has run_len[] inputs
+ * tagged run_value[] (both arrays hold every filter's runs, filter-major, run-minor); the
+ * inputs of a build call are concatenated in the same order. The result -- pages, slots and
+ * descriptor, num_unique included -- is what the reference leaves after adding run 0 onto
+ * old_filter (or onto no filter), run 1 onto that, and so on; value_size is the last run's.
+ * The build, probe, info, image, trim and estimate calls work on the batch as on any other,
+ * and it may be the old filter of a later batch.
+ * EINVAL: a filter's values not strictly increasing, a first value narrower than the old
+ * filter's value_size, a zero-length run, more than rf_amd_max_fingerprints fingerprints (old
+ * filter's included), fingerprint_size + value_size of the last value over 32.
+ * Precondition (not checkable): every value is greater than every value already in the old
+ * filter, as the trunk guarantees (value = base_num_branches + i). */
+int rf_amd_batch_create_runs(rf_amd_engine *e, const rf_amd_config *cfg, uint32_t num_filters,
+                             const uint32_t *num_runs,   /* per filter, >= 1                  */
+                             const uint32_t *run_len,    /* all runs, filter-major, run-minor */
+                             const uint16_t *run_value,  /* same order                        */
+                             rf_amd_batch *const *old_batch, const uint32_t *old_index,
+                             rf_amd_batch **out);
 /* synchronises the device, then releases the batch's memory (routing_filter_dec_ref's
  * release of a superseded filter, src/routing_filter.c:1101-1109) */
 void rf_amd_batch_destroy(rf_amd_batch *b);
@@ -303,6 +323,12 @@ typedef struct rf_amd_image {
 int  rf_amd_filter_add(rf_amd_engine *e, const rf_amd_config *cfg, const rf_amd_image *old_filter,
                        rf_amd_image *filter, const uint32_t *new_fp_arr, uint64_t num_new_fp,
                        uint16_t value);
+/* num_runs chained routing_filter_add calls in one build (rf_amd_batch_create_runs): run j
+ * adds new_fp_arrs[j][0 .. num_new_fp[j]) with values[j] (strictly increasing) onto the
+ * result of run j - 1, run 0 onto old_filter; `filter` is the last filter of the chain */
+int  rf_amd_filter_add_runs(rf_amd_engine *e, const rf_amd_config *cfg, const rf_amd_image *old_filter,
+                            rf_amd_image *filter, const uint32_t *const *new_fp_arrs,
+                            const uint64_t *num_new_fp, const uint16_t *values, uint32_t num_runs);
 /* replaces routing_filter_lookup (src/routing_filter.h:87-92) for a batch of hashed keys */
 int  rf_amd_filter_lookup_hashes(rf_amd_engine *e, const rf_amd_config *cfg,
                                  const rf_amd_image *filter, const uint32_t *hashes, uint64_t n,

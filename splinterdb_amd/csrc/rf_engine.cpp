@@ -305,6 +305,7 @@ struct rf_amd_batch {
   std::vector<uint32_t> pre;  // NUM_PRE x (F + 1)
   uint32_t* pre_of(int k) { return pre.data() + (size_t)k * (F + 1); }
   uint32_t num_tiles = 0, num_old_tiles = 0, num_old_idx = 0;
+  bool chained = false;  // several runs of new inputs per filter (rf_amd_batch_create_runs)
   DevBuf d_pre;
   uint64_t E = 0, keys_total = 0;
   uint32_t CB = 0, I = 0, PS = 0, PF = 0;
@@ -316,7 +317,8 @@ struct rf_amd_batch {
   DevBuf d_plans, d_outs, d_ent, d_part, d_sorted, d_cb_count, d_cb_start, d_cb_cursor, d_cb_filter,
       d_overflow, d_idx_cnt, d_idx_start, d_slots, d_page_first, d_pg_filter, d_pages, d_tile_filter,
       d_tile_start, d_old_tile_filter, d_old_tile_start, d_old_cnt, d_old_pos, d_first_old, d_has_old, d_pplans, d_lines, d_idx_filter, d_spill,
-      d_old_idx_filter, d_old32, d_old_tot, d_ob_lo, d_ob_n, d_pg_noline, d_cb_out, d_lay_wg, d_lay_hand;
+      d_old_idx_filter, d_old32, d_old_tot, d_ob_lo, d_ob_n, d_pg_noline, d_cb_out, d_lay_wg, d_lay_hand,
+      d_tile_value, d_tile_end;  // chained batches: each tile's run value and end
   // K5 over several workgroups per filter (layout_groups): indices per workgroup, the grid of
   // k_layout_seg (0: no filter is split), whether any filter keeps one workgroup, and the
   // sequence number that tags a build's hand-offs (never 0: the words start out zero)
@@ -342,7 +344,7 @@ struct rf_amd_batch {
             &d_pages, &d_tile_filter, &d_tile_start, &d_old_tile_filter, &d_old_tile_start, &d_old_cnt,
             &d_old_pos, &d_first_old, &d_has_old, &d_pplans, &d_lines, &d_idx_filter, &d_spill,
             &d_old_idx_filter, &d_old32, &d_old_tot, &d_ob_lo, &d_ob_n, &d_pg_noline, &d_pre, &d_cb_out,
-            &d_lay_wg, &d_lay_hand};
+            &d_lay_wg, &d_lay_hand, &d_tile_value, &d_tile_end};
   }
 };
 
@@ -506,18 +508,55 @@ static uint32_t line_log_group(uint32_t lis, uint32_t rvs, double lam) {
   return 0;
 }
 
-extern "C" int rf_amd_batch_create(rf_amd_engine* e, const rf_amd_config* cfg, uint32_t num_filters,
-                                   const uint32_t* num_new, const uint16_t* value,
-                                   rf_amd_batch* const* old_batch, const uint32_t* old_index,
-                                   rf_amd_batch** out) {
+// num_indices of a filter of nfp fingerprints (src/routing_filter.c:374-379)
+static uint32_t num_indices_of(uint64_t nfp, uint32_t lis) {
+  uint32_t lnb = 63 - __builtin_clzll(nfp);
+  if (lnb < lis) lnb = lis;
+  return 1u << (lnb - lis);
+}
+
+// rf_amd_batch_create, and rf_amd_batch_create_runs with num_runs != nullptr: filter f's new
+// inputs are then num_runs[f] runs (run_len / run_value, filter-major) and num_new / value are
+// not read. nothing is allocated or launched before the arguments have been checked.
+static int batch_create(rf_amd_engine* e, const rf_amd_config* cfg, uint32_t num_filters,
+                        const uint32_t* num_new, const uint16_t* value, const uint32_t* num_runs,
+                        const uint32_t* run_len, const uint16_t* run_value,
+                        rf_amd_batch* const* old_batch, const uint32_t* old_index, rf_amd_batch** out) {
   if (!e) return fail(RF_AMD_ENODEV, "no engine");
   if (int rc = check_cfg(cfg)) return rc;
-  if (num_filters == 0 || !num_new || !out) return fail(RF_AMD_EINVAL, "empty batch");
+  if (num_filters == 0 || !(num_runs ? (run_len && run_value) : num_new != nullptr) || !out)
+    return fail(RF_AMD_EINVAL, "empty batch");
+  std::vector<uint32_t> run_first(num_filters + 1, 0u), run_total;  // chained: first run, inputs per filter
+  if (num_runs) {
+    run_total.assign(num_filters, 0u);
+    for (uint32_t f = 0; f < num_filters; f++) {
+      if (num_runs[f] == 0) return fail(RF_AMD_EINVAL, "a filter without runs");
+      run_first[f + 1] = run_first[f] + num_runs[f];
+      uint64_t tot = 0;
+      for (uint32_t r = run_first[f]; r < run_first[f + 1]; r++) {
+        if (run_len[r] == 0) return fail(RF_AMD_EINVAL, "zero-length run");
+        if (r > run_first[f] && run_value[r] <= run_value[r - 1])
+          return fail(RF_AMD_EINVAL, "run values of a filter must be strictly increasing");
+        tot += run_len[r];
+      }
+      if (tot > rf_amd_max_fingerprints(cfg))
+        return fail(RF_AMD_EINVAL, "num_fingerprints over routing_filter_max_fingerprints (reference: UB)");
+      if (cfg->fingerprint_size + vsize_of(run_value[run_first[f + 1] - 1]) > 32)
+        return fail(RF_AMD_EINVAL, "fp_size + value_size > 32");
+      const rf_amd_batch* ob = (old_batch && old_batch[f]) ? old_batch[f] : nullptr;
+      const uint32_t oi = old_index ? old_index[f] : 0;
+      if (ob && oi < ob->F && vsize_of(run_value[run_first[f]]) < ob->plans[oi].vs)
+        return fail(RF_AMD_EINVAL, "first run's value narrower than the old filter's value_size");
+      run_total[f] = (uint32_t)tot;
+    }
+    num_new = run_total.data();
+  }
   HIPCHK(hipSetDevice(e->device));
   auto* b = new rf_amd_batch();
   b->eng = e;
   b->cfg = *cfg;
   b->F = num_filters;
+  b->chained = num_runs != nullptr;
   b->plans.resize(num_filters);
   b->pre.assign((size_t)rf_amd_batch::NUM_PRE * (num_filters + 1), 0u);
   const uint32_t lis = cfg->log_index_size, fps = cfg->fingerprint_size, P = cfg->page_size;
@@ -540,7 +579,7 @@ extern "C" int rf_amd_batch_create(rf_amd_engine* e, const rf_amd_config* cfg, u
       op = &ob->plans[oi];
       b->wide = true;
     }
-    const uint32_t v = value ? value[f] : 0;
+    const uint32_t v = num_runs ? run_value[run_first[f + 1] - 1] : value ? value[f] : 0;
     p.num_new = num_new[f];
     p.old_region = op ? op->num_fp : 0;
     const uint64_t nfp = (uint64_t)p.num_new + p.old_region;
@@ -611,9 +650,18 @@ extern "C" int rf_amd_batch_create(rf_amd_engine* e, const rf_amd_config* cfg, u
       p.old_slots = ob->d_slots.as<uint64_t>() + op->idx_base;
       olds[f] = {ob, op};
     }
+    uint32_t ntiles = (p.num_new + TILE_KEYS - 1) / TILE_KEYS;
+    if (num_runs) {
+      // the last chain step's group width (num_unique quirk): from the filter that step starts
+      // from -- the old filter plus every run but the last; tiles end at run boundaries
+      const uint64_t prev_fp = nfp - run_len[run_first[f + 1] - 1];
+      p.npo = prev_fp ? p.num_indices / num_indices_of(prev_fp, lis) : 1u;
+      ntiles = 0;
+      for (uint32_t r = run_first[f]; r < run_first[f + 1]; r++) ntiles += (run_len[r] + TILE_KEYS - 1) / TILE_KEYS;
+    }
     {
       auto pre = [&](int k, uint32_t count) { b->pre_of(k)[f + 1] = b->pre_of(k)[f] + count; };
-      pre(rf_amd_batch::PRE_TILE, (p.num_new + TILE_KEYS - 1) / TILE_KEYS);
+      pre(rf_amd_batch::PRE_TILE, ntiles);
       pre(rf_amd_batch::PRE_OTILE, (p.old_region + TILE_KEYS - 1) / TILE_KEYS);
       pre(rf_amd_batch::PRE_CB, 1u << p.cbits);
       pre(rf_amd_batch::PRE_PG, p.page_cap);
@@ -745,6 +793,10 @@ extern "C" int rf_amd_batch_create(rf_amd_engine* e, const rf_amd_config* cfg, u
   rc |= b->d_pages.alloc((size_t)b->PS * P + 256, pool);
   rc |= b->d_tile_filter.alloc(4ull * b->num_tiles, pool);
   rc |= b->d_tile_start.alloc(4ull * b->num_tiles, pool);
+  if (b->chained) {
+    rc |= b->d_tile_value.alloc(4ull * b->num_tiles, pool);
+    rc |= b->d_tile_end.alloc(4ull * b->num_tiles, pool);
+  }
   rc |= b->d_old_tile_filter.alloc(4ull * b->num_old_tiles, pool);
   rc |= b->d_old_tile_start.alloc(4ull * b->num_old_tiles, pool);
   rc |= b->d_pre.alloc(4 * b->pre.size(), pool);
@@ -752,12 +804,14 @@ extern "C" int rf_amd_batch_create(rf_amd_engine* e, const rf_amd_config* cfg, u
     rc |= b->d_lay_wg.alloc(4ull * b->lay_grid, pool);
     rc |= b->d_lay_hand.alloc(16ull * b->lay_grid, pool);
   }
+  if (b->wide || b->chained) {  // the num_unique quirk's per-index old entries (K4 -> K5)
+    rc |= b->d_first_old.alloc(4 * b->I, pool);
+    rc |= b->d_has_old.alloc(4 * b->I, pool);
+  }
   if (b->wide) {
     rc |= b->d_old_cnt.alloc(4ull * b->num_old_idx, pool);
     rc |= b->d_old_pos.alloc(4ull * b->num_old_idx, pool);
     rc |= b->d_old_idx_filter.alloc(4ull * b->num_old_idx, pool);
-    rc |= b->d_first_old.alloc(4 * b->I, pool);
-    rc |= b->d_has_old.alloc(4 * b->I, pool);
     if (b->flag32) {
       rc |= b->d_old32.alloc(4 * b->old_total + 64, pool);
       rc |= b->d_old_tot.alloc(4 * b->F, pool);
@@ -798,6 +852,29 @@ extern "C" int rf_amd_batch_create(rf_amd_engine* e, const rf_amd_config* cfg, u
   UP(b->d_pplans, pp);
   UP(b->d_pre, b->pre);
   UP(b->d_lay_wg, lay_wg);
+  // tile maps of a chained batch, built here: tiles are cut at run boundaries and carry their
+  // run's value and end (both relative to the filter's first input, like tile_start)
+  std::vector<uint32_t> tf, ts, tv, te;
+  if (b->chained) {
+    for (std::vector<uint32_t>* v : {&tf, &ts, &tv, &te}) v->reserve(b->num_tiles);
+    for (uint32_t f = 0; f < num_filters; f++) {
+      uint32_t first = 0;
+      for (uint32_t r = run_first[f]; r < run_first[f + 1]; r++) {
+        const uint32_t end = first + run_len[r];
+        for (uint32_t s0 = first; s0 < end; s0 += TILE_KEYS) {
+          tf.push_back(f);
+          ts.push_back(s0);
+          tv.push_back(run_value[r]);
+          te.push_back(std::min(end, s0 + (uint32_t)TILE_KEYS));
+        }
+        first = end;
+      }
+    }
+    UP(b->d_tile_filter, tf);
+    UP(b->d_tile_start, ts);
+    UP(b->d_tile_value, tv);
+    UP(b->d_tile_end, te);
+  }
 #undef UP
   // hand-off tags start out zero, once per batch: a build's tag is never 0
   if (b->lay_grid) HIPCHK(hipMemsetAsync(b->d_lay_hand.p, 0, 16ull * b->lay_grid, st));
@@ -815,6 +892,7 @@ extern "C" int rf_amd_batch_create(rf_amd_engine* e, const rf_amd_config* cfg, u
     for (const M& m : maps) {
       const uint32_t n = b->pre_of(m.k)[num_filters];
       if (n == 0 || !m.fof->p) continue;
+      if (b->chained && m.k == rf_amd_batch::PRE_TILE) continue;  // uploaded above
       if (rf_launch_seg_fill(st, dp + (size_t)m.k * F1, num_filters, n, m.fof->as<uint32_t>(),
                              m.start ? m.start->as<uint32_t>() : nullptr, TILE_KEYS)) {
         delete b;
@@ -827,6 +905,29 @@ extern "C" int rf_amd_batch_create(rf_amd_engine* e, const rf_amd_config* cfg, u
   pool_trace("create sync", 0, ts0);
   *out = b;
   return 0;
+}
+
+extern "C" int rf_amd_batch_create(rf_amd_engine* e, const rf_amd_config* cfg, uint32_t num_filters,
+                                   const uint32_t* num_new, const uint16_t* value,
+                                   rf_amd_batch* const* old_batch, const uint32_t* old_index,
+                                   rf_amd_batch** out) {
+  return batch_create(e, cfg, num_filters, num_new, value, nullptr, nullptr, nullptr, old_batch, old_index, out);
+}
+
+extern "C" int rf_amd_batch_create_runs(rf_amd_engine* e, const rf_amd_config* cfg, uint32_t num_filters,
+                                        const uint32_t* num_runs, const uint32_t* run_len,
+                                        const uint16_t* run_value, rf_amd_batch* const* old_batch,
+                                        const uint32_t* old_index, rf_amd_batch** out) {
+  if (!num_runs || !run_len || !run_value) return fail(RF_AMD_EINVAL, "null run arrays");
+  // one run per filter: exactly rf_amd_batch_create (runs and filters then share their index)
+  bool single = true;
+  for (uint32_t f = 0; f < num_filters && single; f++) single = num_runs[f] == 1;
+  if (single) {
+    for (uint32_t f = 0; f < num_filters; f++)
+      if (run_len[f] == 0) return fail(RF_AMD_EINVAL, "zero-length run");
+    return batch_create(e, cfg, num_filters, run_len, run_value, nullptr, nullptr, nullptr, old_batch, old_index, out);
+  }
+  return batch_create(e, cfg, num_filters, nullptr, nullptr, num_runs, run_len, run_value, old_batch, old_index, out);
 }
 
 extern "C" void rf_amd_batch_destroy(rf_amd_batch* b) {
@@ -1096,6 +1197,8 @@ static LaunchArgs make_args(rf_amd_batch* b, hipStream_t st) {
   a.tile_filter = b->d_tile_filter.as<uint32_t>();
   a.tile_start = b->d_tile_start.as<uint32_t>();
   a.num_tiles = b->num_tiles;
+  a.tile_value = b->chained ? b->d_tile_value.as<uint32_t>() : nullptr;
+  a.tile_end = b->chained ? b->d_tile_end.as<uint32_t>() : nullptr;
   a.old_tile_filter = b->d_old_tile_filter.as<uint32_t>();
   a.old_tile_start = b->d_old_tile_start.as<uint32_t>();
   a.num_old_tiles = b->num_old_tiles;
@@ -2589,30 +2692,46 @@ extern "C" int rf_amd_batch_import(rf_amd_engine* e, const rf_amd_config* cfg, u
                       device_resident ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, out);
 }
 
-extern "C" int rf_amd_filter_add(rf_amd_engine* e, const rf_amd_config* cfg, const rf_amd_image* old_filter,
-                                 rf_amd_image* filter, const uint32_t* new_fp_arr, uint64_t num_new_fp,
-                                 uint16_t value) {
+// rf_amd_filter_add (num_runs == 0: the one run new_fp_arrs[0], num_new_fp[0], values[0], which
+// may be empty) and rf_amd_filter_add_runs
+static int filter_add_runs(rf_amd_engine* e, const rf_amd_config* cfg, const rf_amd_image* old_filter,
+                           rf_amd_image* filter, const uint32_t* const* new_fp_arrs, const uint64_t* num_new_fp,
+                           const uint16_t* values, uint32_t num_runs) {
   if (!e) return fail(RF_AMD_ENODEV, "no engine");
   if (!filter) return fail(RF_AMD_EINVAL, "null filter out-param");
   memset(filter, 0, sizeof(*filter));
-  if (num_new_fp && !new_fp_arr) return fail(RF_AMD_EINVAL, "null fingerprint array");
-  if (num_new_fp > 0xffffffffull) return fail(RF_AMD_EINVAL, "too many fingerprints");
+  const uint32_t k = num_runs ? num_runs : 1u;
+  std::vector<uint32_t> lens(k);
+  uint64_t total = 0;
+  for (uint32_t j = 0; j < k; j++) {
+    if (num_new_fp[j] && !new_fp_arrs[j]) return fail(RF_AMD_EINVAL, "null fingerprint array");
+    if (num_new_fp[j] > 0xffffffffull) return fail(RF_AMD_EINVAL, "too many fingerprints");
+    lens[j] = (uint32_t)num_new_fp[j];
+    total += num_new_fp[j];
+  }
   rf_amd_batch* ob = nullptr;
   const bool has_old = old_filter && old_filter->pages && old_filter->info.num_fingerprints;
   if (has_old)
     if (int rc = batch_from_image(e, cfg, old_filter, &ob)) return rc;
   rf_amd_batch* b = nullptr;
-  const uint32_t n32 = (uint32_t)num_new_fp;
   uint32_t zero = 0;
-  int rc = rf_amd_batch_create(e, cfg, 1, &n32, &value, has_old ? &ob : nullptr, has_old ? &zero : nullptr, &b);
+  int rc = num_runs ? rf_amd_batch_create_runs(e, cfg, 1, &num_runs, lens.data(), values, has_old ? &ob : nullptr,
+                                               has_old ? &zero : nullptr, &b)
+                    : rf_amd_batch_create(e, cfg, 1, lens.data(), values, has_old ? &ob : nullptr,
+                                          has_old ? &zero : nullptr, &b);
   if (rc) {
     rf_amd_batch_destroy(ob);
     return rc;
   }
   DevBuf d_h;
-  if ((rc = d_h.alloc(4ull * num_new_fp + 16)) == 0) {
-    hipError_t he = hipMemcpyAsync(d_h.p, new_fp_arr, 4ull * num_new_fp, hipMemcpyHostToDevice, e->stream);
-    if (he != hipSuccess) rc = fail(RF_AMD_EINVAL, "H2D failed");
+  if ((rc = d_h.alloc(4ull * total + 16)) == 0) {
+    uint64_t at = 0;
+    for (uint32_t j = 0; j < k && !rc; j++) {
+      if (lens[j] && hipMemcpyAsync(d_h.as<uint32_t>() + at, new_fp_arrs[j], 4ull * lens[j], hipMemcpyHostToDevice,
+                                    e->stream) != hipSuccess)
+        rc = fail(RF_AMD_EINVAL, "H2D failed");
+      at += lens[j];
+    }
   }
   if (!rc) rc = rf_amd_batch_build_hashes(b, d_h.as<uint32_t>(), nullptr);
   rf_amd_filter_info info{};
@@ -2630,6 +2749,19 @@ extern "C" int rf_amd_filter_add(rf_amd_engine* e, const rf_amd_config* cfg, con
   rf_amd_batch_destroy(b);
   rf_amd_batch_destroy(ob);
   return rc;
+}
+
+extern "C" int rf_amd_filter_add(rf_amd_engine* e, const rf_amd_config* cfg, const rf_amd_image* old_filter,
+                                 rf_amd_image* filter, const uint32_t* new_fp_arr, uint64_t num_new_fp,
+                                 uint16_t value) {
+  return filter_add_runs(e, cfg, old_filter, filter, &new_fp_arr, &num_new_fp, &value, 0);
+}
+
+extern "C" int rf_amd_filter_add_runs(rf_amd_engine* e, const rf_amd_config* cfg, const rf_amd_image* old_filter,
+                                      rf_amd_image* filter, const uint32_t* const* new_fp_arrs,
+                                      const uint64_t* num_new_fp, const uint16_t* values, uint32_t num_runs) {
+  if (!num_runs || !new_fp_arrs || !num_new_fp || !values) return fail(RF_AMD_EINVAL, "null / empty runs");
+  return filter_add_runs(e, cfg, old_filter, filter, new_fp_arrs, num_new_fp, values, num_runs);
 }
 
 extern "C" int rf_amd_filter_lookup_hashes(rf_amd_engine* e, const rf_amd_config* cfg, const rf_amd_image* filter,

@@ -125,6 +125,15 @@ __device__ __forceinline__ void cb_scan_filter(const FilterPlan& P, const uint32
   }
 }
 
+// Chained batches (rf_amd_batch_create_runs): a filter's new inputs are several runs, each
+// tagged with its own value. Tiles are cut at run boundaries, so a tile belongs to one run:
+// value[t] is its run's value and end[t] its end (like tile_start, relative to the filter's
+// first input). Read only by the RUNS instantiations; single-run batches pass {}.
+struct TileRuns {
+  const uint32_t* value;
+  const uint32_t* end;
+};
+
 // what the gated K1 of a fused build does besides counting ({}: nothing)
 struct CountFold {
   uint32_t* outs_words;    // the batch's FilterOut words, zeroed here when no init launch ran
@@ -138,7 +147,7 @@ struct CountFold {
 // ======================================================================================
 // K1: hash + coarse-bucket histogram
 // ======================================================================================
-template <int KIND, typename EntT, bool FL = (sizeof(EntT) == 8)>
+template <int KIND, typename EntT, bool FL = (sizeof(EntT) == 8), bool RUNS = false>
 __global__ __launch_bounds__(TILE_NT) void k_hash_count(const FilterPlan* __restrict__ plans,
                                                         const uint32_t* __restrict__ tile_filter,
                                                         const uint32_t* __restrict__ tile_start,
@@ -148,7 +157,7 @@ __global__ __launch_bounds__(TILE_NT) void k_hash_count(const FilterPlan* __rest
                                                         uint32_t seed, EntT* __restrict__ ent,
                                                         uint32_t* cb_count,
                                                         const uint32_t* __restrict__ gate, uint32_t num_tiles,
-                                                        CountFold fold) {
+                                                        CountFold fold, TileRuns runs) {
   __shared__ uint32_t s_hist[MAX_CB];
   // a build that follows a clean one has no init launch: its outs are zeroed here, before
   // K4 adds to them (this launch comes before K4 whether or not the partition spilled)
@@ -159,7 +168,8 @@ __global__ __launch_bounds__(TILE_NT) void k_hash_count(const FilterPlan* __rest
   for (uint32_t t = blockIdx.x; t < num_tiles; t += gridDim.x) {
   const FilterPlan& P = plans[tile_filter[t]];
   const uint32_t start = tile_start[t];
-  const uint32_t count = min((uint32_t)TILE_KEYS, P.num_new - start);
+  const uint32_t count = RUNS ? runs.end[t] - start : min((uint32_t)TILE_KEYS, P.num_new - start);
+  const uint32_t value = RUNS ? runs.value[t] : P.value;
   const uint32_t num_cb = 1u << P.cbits;
   __syncthreads();  // the previous tile's histogram has been flushed
   for (uint32_t i = threadIdx.x; i < num_cb; i += TILE_NT) s_hist[i] = 0;
@@ -167,7 +177,7 @@ __global__ __launch_bounds__(TILE_NT) void k_hash_count(const FilterPlan* __rest
   const uint32_t esh = fp_size + P.vs - P.cbits;  // entry >> esh = coarse bucket
   for (uint32_t j = threadIdx.x; j < count; j += TILE_NT) {
     const uint32_t h = hash_key<KIND>(in0, offs, key_len, seed, P.key_first + start + j);
-    const uint32_t e = ((h >> (32 - fp_size)) << P.vs) | P.value;
+    const uint32_t e = ((h >> (32 - fp_size)) << P.vs) | value;
     if constexpr (FL) {
       ent[P.e_first + start + j] = (EntT)(((EntT)e << 1) | EntT(1));  // new entry: flag 1
     } else {
@@ -245,7 +255,7 @@ __global__ __launch_bounds__(256) void k_cb_scan(const FilterPlan* __restrict__ 
 // ======================================================================================
 // K3: scatter entries into coarse buckets
 // ======================================================================================
-template <typename EntT, bool FL = (sizeof(EntT) == 8)>
+template <typename EntT, bool FL = (sizeof(EntT) == 8), bool RUNS = false>
 __global__ __launch_bounds__(SCAT_NT) void k_scatter(const FilterPlan* __restrict__ plans,
                                                      const uint32_t* __restrict__ tile_filter,
                                                      const uint32_t* __restrict__ tile_start,
@@ -253,7 +263,8 @@ __global__ __launch_bounds__(SCAT_NT) void k_scatter(const FilterPlan* __restric
                                                      const EntT* __restrict__ ent,
                                                      EntT* __restrict__ part,
                                                      uint32_t* __restrict__ cb_cursor,
-                                                     const uint32_t* __restrict__ gate, uint32_t num_tiles) {
+                                                     const uint32_t* __restrict__ gate, uint32_t num_tiles,
+                                                     TileRuns runs) {
   // The tile is sorted by coarse bucket in LDS, then each bucket's run is written by
   // consecutive lanes: whole 64-byte granules instead of scattered 4-byte stores.
   __shared__ EntT s_stage[TILE_KEYS];
@@ -269,7 +280,8 @@ __global__ __launch_bounds__(SCAT_NT) void k_scatter(const FilterPlan* __restric
   const uint32_t start = tile_start[t];
   const uint32_t region = region_is_old ? P.old_region : P.num_new;
   const uint64_t base = P.e_first + (region_is_old ? P.num_new : 0u) + start;
-  const uint32_t count = min((uint32_t)TILE_KEYS, region - start);
+  // (the old region of a chained batch is tiled like any other: only new tiles end at a run's end)
+  const uint32_t count = (RUNS && !region_is_old) ? runs.end[t] - start : min((uint32_t)TILE_KEYS, region - start);
   const uint32_t num_cb = 1u << P.cbits;
   for (uint32_t i = threadIdx.x; i < num_cb; i += SCAT_NT) s_off[i] = 0;
   __syncthreads();
@@ -382,7 +394,8 @@ extern "C" int rf_debug_set_phase_buffer(uint64_t* d_buf, uint32_t kid) {
 #define RF_SCAT_X3 1
 #endif
 // FL (32-bit incremental builds): the entries are written flagged new, (e << 1) | 1.
-template <int KIND, bool FL = false>
+// RUNS (chained batches): the tile's value and end come from its run (TileRuns).
+template <int KIND, bool FL = false, bool RUNS = false>
 __global__ __launch_bounds__(SCAT_NT) __attribute__((amdgpu_waves_per_eu(RF_SCAT_WPE))) void k_hash_scatter(const FilterPlan* __restrict__ plans,
                                                           const uint32_t* __restrict__ tile_filter,
                                                           const uint32_t* __restrict__ tile_start,
@@ -391,7 +404,7 @@ __global__ __launch_bounds__(SCAT_NT) __attribute__((amdgpu_waves_per_eu(RF_SCAT
                                                           uint32_t key_len, uint32_t fp_size, uint32_t seed,
                                                           uint32_t* __restrict__ part,
                                                           uint32_t* __restrict__ cb_fill,
-                                                          uint32_t* __restrict__ spill) {
+                                                          uint32_t* __restrict__ spill, TileRuns runs) {
   __shared__ __attribute__((aligned(16))) uint32_t s_stage[TILE_KEYS];
   __shared__ uint32_t s_off[MAX_CB];  // local counts -> local starts -> (global slot - local start)
   __shared__ uint32_t s_tmp[SCAT_NT / WAVE + 1];
@@ -401,7 +414,8 @@ __global__ __launch_bounds__(SCAT_NT) __attribute__((amdgpu_waves_per_eu(RF_SCAT
   const uint32_t t = xcd_chunk(blockIdx.x, gridDim.x);  // a filter's tiles share an XCD
   const FilterPlan& P = plans[tile_filter[t]];
   const uint32_t start = tile_start[t];
-  const uint32_t count = min((uint32_t)TILE_KEYS, P.num_new - start);
+  const uint32_t count = RUNS ? runs.end[t] - start : min((uint32_t)TILE_KEYS, P.num_new - start);
+  const uint32_t value = RUNS ? runs.value[t] : P.value;  // workgroup-uniform either way
   const uint32_t num_cb = 1u << P.cbits;
   for (uint32_t i = threadIdx.x; i < num_cb; i += SCAT_NT) s_off[i] = 0;
   __syncthreads();
@@ -466,7 +480,7 @@ __global__ __launch_bounds__(SCAT_NT) __attribute__((amdgpu_waves_per_eu(RF_SCAT
           w[3 + q] = half ? b[k][q] : recv;
         }
         const uint32_t h = xxh32_24(w, seed);
-        v[k0 + k] = ((((h >> (32 - fp_size)) << P.vs) | P.value) << flag) | flag;
+        v[k0 + k] = ((((h >> (32 - fp_size)) << P.vs) | value) << flag) | flag;
       }
     } else if constexpr (KIND == IN_KEYS24) {
       // 24-byte keys: issue all of the chunk's loads, then hash (z depends on every loaded
@@ -491,7 +505,7 @@ __global__ __launch_bounds__(SCAT_NT) __attribute__((amdgpu_waves_per_eu(RF_SCAT
       for (int k = 0; k < HASH_CHUNK; k++) {
         uint32_t w[6] = {ka[k].x + z, ka[k].y, kb[k].x, kb[k].y, kc[k].x, kc[k].y};
         const uint32_t h = xxh32_24(w, seed);
-        v[k0 + k] = ((((h >> (32 - fp_size)) << P.vs) | P.value) << flag) | flag;
+        v[k0 + k] = ((((h >> (32 - fp_size)) << P.vs) | value) << flag) | flag;
       }
     } else if constexpr (KIND == IN_VAR) {
       // variable-length keys: this wave's keys [wave * 64 * PER, +64 * PER) are one
@@ -509,14 +523,14 @@ __global__ __launch_bounds__(SCAT_NT) __attribute__((amdgpu_waves_per_eu(RF_SCAT
         }
         const uint32_t h = wave_hash_var<VWIN, false>(static_cast<const uint8_t*>(in0), o0, o1,
                                                       key_of(k0 + k) < count, s_vwin, seed, &vw0, &vw1);
-        v[k0 + k] = ((((h >> (32 - fp_size)) << P.vs) | P.value) << flag) | flag;
+        v[k0 + k] = ((((h >> (32 - fp_size)) << P.vs) | value) << flag) | flag;
       }
     } else {
 #pragma unroll
       for (int k = k0; k < k0 + HASH_CHUNK; k++) {
         const uint32_t j = min(threadIdx.x + k * SCAT_NT, count - 1) + dep;
         const uint32_t h = hash_key<KIND>(in0, offs, key_len, seed, P.key_first + start + j);
-        v[k] = ((((h >> (32 - fp_size)) << P.vs) | P.value) << flag) | flag;
+        v[k] = ((((h >> (32 - fp_size)) << P.vs) | value) << flag) | flag;
       }
     }
     static_assert(HASH_CHUNK == 8, "opaque dependency below takes 8 hashes");
@@ -700,7 +714,11 @@ __device__ __forceinline__ void write_index_bounds(const CbCtx& c, const uint32_
 // (s_b[nn, n)), and the dedupe pass reads the two sorted runs through a merge path. Old
 // flagged values are even and new ones odd, so no old value equals a new one and the merge
 // yields exactly the order a sort of all n would (old first on equal e).
-template <typename EntT, bool FL = (sizeof(EntT) == 8), bool DUAL = false, bool LIST = false>
+// RUNS (chained batches, several runs of new entries with increasing values per filter): for
+// the num_unique quirk an "old" entry is one that is not of the last run -- the old filter's
+// entries and those of the earlier runs -- told by its value field (!= P.value, the last
+// run's), also where entries carry no flag; P.npo is the last chain step's.
+template <typename EntT, bool FL = (sizeof(EntT) == 8), bool DUAL = false, bool LIST = false, bool RUNS = false>
 __global__ __launch_bounds__(SORT_NT, 6) void k_cb_sort(const FilterPlan* __restrict__ plans,
                                                      const uint32_t* __restrict__ cb_filter,
                                                      const uint32_t* __restrict__ cb_count,
@@ -939,7 +957,7 @@ __global__ __launch_bounds__(SORT_NT, 6) void k_cb_sort(const FilterPlan* __rest
   }
   // incremental builds that split old indices (npo > 1) need each index's smallest old entry
   // for K5's num_unique put-back quirk; with one new index per old index nothing reads it
-  const bool track_old = FL && P.npo > 1;
+  const bool track_old = (FL || RUNS) && P.npo > 1;
   if (track_old) {  // s_bin is no longer read; the scan below orders these before use
     for (uint32_t i = threadIdx.x; i < ipc; i += SORT_NT) { s_fo[i] = 0xffffffffu; s_ho[i] = 0; }
   }
@@ -1018,12 +1036,20 @@ __global__ __launch_bounds__(SORT_NT, 6) void k_cb_sort(const FilterPlan* __rest
         for (uint32_t l = lprev + 1; l <= li; l++) s_first[l] = pos;  // lprev NONE: from 0
         uniq += (fp != (li != lprev ? (0xffffffffu >> P.vs) : fprev)) ? 1u : 0u;
         pos++;
-        if constexpr (FL) {
+        if constexpr (FL || RUNS) {
           // old entry: remember each index's smallest (num_unique quirk). The run is in
           // order, so its first old entry of an index is its smallest there: one LDS atomic
           // per (run, index) instead of one per old entry (all of an index's entries would
           // otherwise contend for one address)
-          if (track_old && !(w[k] & EntT(1)) && li != fo_li) {
+          if constexpr (RUNS) {
+            bool is_old = (e & ((1u << P.vs) - 1u)) != P.value;  // not of the last run
+            if constexpr (FL) is_old = is_old || !(w[k] & EntT(1));
+            if (track_old && is_old && li != fo_li) {
+              atomicMin(&s_fo[li], e);
+              s_ho[li] = 1;
+              fo_li = li;
+            }
+          } else if (track_old && !(w[k] & EntT(1)) && li != fo_li) {
             atomicMin(&s_fo[li], e);
             s_ho[li] = 1;
             fo_li = li;
@@ -1083,6 +1109,10 @@ __global__ __launch_bounds__(SORT_NT, 6) void k_cb_sort(const FilterPlan* __rest
 constexpr uint32_t MRG_NEW_CAP = 2048;
 constexpr uint32_t MRG_LNB_MAX = 9;  // at most 512 bins
 constexpr uint32_t MRG_RUN = (SORT_CAP + SORT_NT - 1) / SORT_NT + 1;  // output slots per thread (odd)
+// RUNS (chained batches): new entries of the runs before the last are "old" for the num_unique
+// quirk too (see k_cb_sort); such an entry may precede this thread's share unseen, so each
+// index's smallest is taken with an LDS atomic minimum.
+template <bool RUNS = false>
 __global__ __launch_bounds__(SORT_NT, 6) void k_cb_merge(const FilterPlan* __restrict__ plans,
                                                       const uint32_t* __restrict__ cb_filter,
                                                       const uint32_t* __restrict__ cb_count,
@@ -1334,7 +1364,12 @@ __global__ __launch_bounds__(SORT_NT, 6) void k_cb_merge(const FilterPlan* __res
         const bool first = li != pli;  // pli NONE: no predecessor
         uniq += fp != (first ? (0xffffffffu >> vs) : pfp) ? 1u : 0u;
         if (first) s_start[li] = sl;
-        if (track_old && take_old) {
+        if constexpr (RUNS) {
+          if (track_old && (take_old || (e & ((1u << vs) - 1u)) != P.value)) {
+            if (li != pold || k == 0) atomicMin(&s_fo[li], e);
+            pold = li;
+          }
+        } else if (track_old && take_old) {
           if (li != pold) s_fo[li] = e;
           pold = li;
         }
@@ -1388,7 +1423,7 @@ __global__ __launch_bounds__(SORT_NT, 6) void k_cb_merge(const FilterPlan* __res
 
 // K4b: coarse buckets larger than LDS (duplicate-heavy inputs). One workgroup per listed
 // bucket, working in global memory: `scratch` is the K1 entry array (free after K3).
-template <typename EntT, bool FL = (sizeof(EntT) == 8), bool DUAL = false>
+template <typename EntT, bool FL = (sizeof(EntT) == 8), bool DUAL = false, bool RUNS = false>
 __global__ __launch_bounds__(BIG_NT) void k_cb_sort_big(const FilterPlan* __restrict__ plans,
                                                         const uint32_t* __restrict__ cb_filter,
                                                         const uint32_t* __restrict__ cb_count,
@@ -1500,8 +1535,15 @@ __global__ __launch_bounds__(BIG_NT) void k_cb_sort_big(const FilterPlan* __rest
       const uint32_t run = s_run;
       if (keep) {
         dst[run + p] = ent_e<EntT, FL>(x);
-        if constexpr (FL) {
-          if (!(x & EntT(1))) {
+        if constexpr (FL || RUNS) {
+          bool is_old;
+          if constexpr (RUNS) {
+            is_old = (ent_e<EntT, FL>(x) & ((1u << P.vs) - 1u)) != P.value;  // not of the last run
+            if constexpr (FL) is_old = is_old || !(x & EntT(1));
+          } else {
+            is_old = !(x & EntT(1));
+          }
+          if (is_old) {
             const uint32_t e = ent_e<EntT, FL>(x);
             const uint32_t li = ish >= 32 ? 0u : ((e >> ish) & (ipc - 1));
             atomicMin(&s_fo[li], e);
@@ -1514,7 +1556,7 @@ __global__ __launch_bounds__(BIG_NT) void k_cb_sort_big(const FilterPlan* __rest
       __syncthreads();
     }
     const uint32_t kept = s_run;
-    if constexpr (FL) {
+    if constexpr (FL || RUNS) {
       for (uint32_t i = threadIdx.x; i < ipc; i += BIG_NT) {
         first_old[c.idx0 + i] = s_fo[i];
         has_old[c.idx0 + i] = s_ho[i];
@@ -4415,30 +4457,33 @@ extern "C" int rf_launch_probe_groups(void* stream, const uint32_t* in, const Pr
 // that strides over the tiles: most of their cost was dispatching one workgroup per tile
 constexpr uint32_t GATED_GRID = 256;
 
-template <typename EntT, bool FL = (sizeof(EntT) == 8)>
+template <typename EntT, bool FL = (sizeof(EntT) == 8), bool RUNS = false>
 static int launch_hash_count_t(const LaunchArgs& a, EntT* ent, uint32_t* counts, const uint32_t* gate,
                                const CountFold& fold) {
   dim3 g(gate ? min(a.num_tiles, GATED_GRID) : a.num_tiles), b(TILE_NT);
-#define L(K) hipLaunchKernelGGL((k_hash_count<K, EntT, FL>), g, b, 0, (hipStream_t)a.stream, a.plans, a.tile_filter, \
-                                a.tile_start, a.in0, a.offs, a.key_len, a.fp_size, a.seed, ent, counts, gate, a.num_tiles, fold)
+  const TileRuns runs{a.tile_value, a.tile_end};
+#define L(K) hipLaunchKernelGGL((k_hash_count<K, EntT, FL, RUNS>), g, b, 0, (hipStream_t)a.stream, a.plans, a.tile_filter, \
+                                a.tile_start, a.in0, a.offs, a.key_len, a.fp_size, a.seed, ent, counts, gate, a.num_tiles, fold, \
+                                runs)
   KIND_SWITCH(a.kind, L);
 #undef L
   CHECK_LAUNCH();
   return 0;
 }
 
-template <typename EntT, bool FL = (sizeof(EntT) == 8)>
+template <typename EntT, bool FL = (sizeof(EntT) == 8), bool RUNS = false>
 static int launch_scatter_t(const LaunchArgs& a, EntT* ent, EntT* part, const uint32_t* gate) {
+  const TileRuns runs{a.tile_value, a.tile_end};
   if (a.num_tiles) {
-    hipLaunchKernelGGL((k_scatter<EntT, FL>), dim3(gate ? min(a.num_tiles, GATED_GRID) : a.num_tiles), dim3(SCAT_NT), 0,
+    hipLaunchKernelGGL((k_scatter<EntT, FL, RUNS>), dim3(gate ? min(a.num_tiles, GATED_GRID) : a.num_tiles), dim3(SCAT_NT), 0,
                        (hipStream_t)a.stream, a.plans, a.tile_filter, a.tile_start, 0u, a.fp_size, ent, part,
-                       a.cb_cursor, gate, a.num_tiles);
+                       a.cb_cursor, gate, a.num_tiles, runs);
     CHECK_LAUNCH();
   }
   if (a.num_old_tiles && !a.flag32) {  // 32-bit incremental builds read the old runs in K4
-    hipLaunchKernelGGL((k_scatter<EntT, FL>), dim3(gate ? min(a.num_old_tiles, GATED_GRID) : a.num_old_tiles),
+    hipLaunchKernelGGL((k_scatter<EntT, FL, RUNS>), dim3(gate ? min(a.num_old_tiles, GATED_GRID) : a.num_old_tiles),
                        dim3(SCAT_NT), 0, (hipStream_t)a.stream, a.plans, a.old_tile_filter, a.old_tile_start, 1u,
-                       a.fp_size, ent, part, a.cb_cursor, gate, a.num_old_tiles);
+                       a.fp_size, ent, part, a.cb_cursor, gate, a.num_old_tiles, runs);
     CHECK_LAUNCH();
   }
   return 0;
@@ -4455,32 +4500,32 @@ static bool k4m_enabled() {
   return v != 0;
 }
 
-template <typename EntT, bool FL = (sizeof(EntT) == 8), bool DUAL = false>
+template <typename EntT, bool FL = (sizeof(EntT) == 8), bool DUAL = false, bool RUNS = false>
 static int launch_sort_t(const LaunchArgs& a, EntT* ent, EntT* part, const uint32_t* spill) {
   bool merged = false;
   if constexpr (DUAL) {
     if (k4m_enabled()) {
       merged = true;
-      hipLaunchKernelGGL(k_cb_merge, dim3(a.num_cb), dim3(SORT_NT), 0, (hipStream_t)a.stream, a.plans, a.cb_filter,
+      hipLaunchKernelGGL((k_cb_merge<RUNS>), dim3(a.num_cb), dim3(SORT_NT), 0, (hipStream_t)a.stream, a.plans, a.cb_filter,
                        a.cb_count, a.cb_start, (const uint32_t*)part, a.old32, a.ob_lo, a.ob_n, a.sorted32, a.idx_cnt,
                        a.idx_start, a.outs, a.overflow, a.lis, a.first_old, a.has_old, spill, a.cb_outs);
       CHECK_LAUNCH();
       // the buckets K4m handed back (bit 31 on their overflow-list entry): up to one workgroup
       // per coarse bucket (early chain rounds hand back nearly all of them); the surplus exits
-      hipLaunchKernelGGL((k_cb_sort<EntT, FL, DUAL, true>), dim3(a.num_cb), dim3(SORT_NT), 0, (hipStream_t)a.stream,
+      hipLaunchKernelGGL((k_cb_sort<EntT, FL, DUAL, true, RUNS>), dim3(a.num_cb), dim3(SORT_NT), 0, (hipStream_t)a.stream,
                          a.plans, a.cb_filter, a.cb_count, a.cb_start, part, a.old32, a.ob_lo, a.ob_n, a.sorted32,
                          a.idx_cnt, a.idx_start, a.outs, a.overflow, a.lis, a.first_old, a.has_old, spill, a.cb_outs,
                          a.overflow);
     }
   }
   if (!merged) {
-    hipLaunchKernelGGL((k_cb_sort<EntT, FL, DUAL>), dim3(a.num_cb), dim3(SORT_NT), 0, (hipStream_t)a.stream, a.plans,
+    hipLaunchKernelGGL((k_cb_sort<EntT, FL, DUAL, false, RUNS>), dim3(a.num_cb), dim3(SORT_NT), 0, (hipStream_t)a.stream, a.plans,
                        a.cb_filter, a.cb_count, a.cb_start, part, a.old32, a.ob_lo, a.ob_n, a.sorted32, a.idx_cnt,
                        a.idx_start, a.outs, a.overflow, a.lis, a.first_old, a.has_old, spill, a.cb_outs, nullptr);
   }
   CHECK_LAUNCH();
   REC(EV_B_SORT);
-  hipLaunchKernelGGL((k_cb_sort_big<EntT, FL, DUAL>), dim3(BIG_GRID), dim3(BIG_NT), 0, (hipStream_t)a.stream, a.plans,
+  hipLaunchKernelGGL((k_cb_sort_big<EntT, FL, DUAL, RUNS>), dim3(BIG_GRID), dim3(BIG_NT), 0, (hipStream_t)a.stream, a.plans,
                      a.cb_filter, a.cb_count, a.cb_start, part, a.old32, a.ob_lo, a.ob_n, ent, a.sorted32, a.idx_cnt, a.idx_start, a.outs,
                      a.overflow, a.lis, a.first_old, a.has_old, spill, a.cb_outs);
   CHECK_LAUNCH();
@@ -4491,8 +4536,11 @@ static int launch_sort_t(const LaunchArgs& a, EntT* ent, EntT* part, const uint3
 extern "C" int rf_launch_plines(const LaunchArgs* pa);
 static int launch_plines_list(const LaunchArgs& a);
 
-extern "C" int rf_launch_build(const LaunchArgs* pa) {
-  const LaunchArgs& a = *pa;
+// RUNS: a chained batch (a.tile_value / a.tile_end set): the tiles carry their run's value and
+// end, and the bucket sorts track the quirk's old entries by value (see k_cb_sort)
+template <bool RUNS>
+static int launch_build_t(const LaunchArgs& a) {
+  const TileRuns runs{a.tile_value, a.tile_end};
   if (a.wide && a.flag32) {
     // incremental add, 32-bit flagged entries (fp_size + value_size <= 31): the new entries
     // are hashed, counted and scattered; each coarse bucket's run of the (sorted) old
@@ -4504,9 +4552,9 @@ extern "C" int rf_launch_build(const LaunchArgs* pa) {
     uint32_t* ent = (uint32_t*)a.ent;
     uint32_t* part = (uint32_t*)a.part;
     if (a.num_tiles) {
-#define L(K) hipLaunchKernelGGL((k_hash_scatter<K, true>), dim3(a.num_tiles), dim3(SCAT_NT), 0, (hipStream_t)a.stream, \
+#define L(K) hipLaunchKernelGGL((k_hash_scatter<K, true, RUNS>), dim3(a.num_tiles), dim3(SCAT_NT), 0, (hipStream_t)a.stream, \
                                 a.plans, a.tile_filter, a.tile_start, a.in0, a.offs, a.key_len, a.fp_size, a.seed, \
-                                part, a.cb_count, a.spill)
+                                part, a.cb_count, a.spill, runs)
       KIND_SWITCH(a.kind, L);
 #undef L
       CHECK_LAUNCH();
@@ -4515,9 +4563,9 @@ extern "C" int rf_launch_build(const LaunchArgs* pa) {
     // workgroup to finish them, the packed starts (K2 folded into K1); scatter
     if (a.num_tiles) {
       const CountFold fold{nullptr, 0, a.spill + 1, a.cb_count, a.cb_start, a.num_filters};
-      if (int rc = launch_hash_count_t<uint32_t, true>(a, ent, a.cb_cursor, a.spill, fold)) return rc;
+      if (int rc = launch_hash_count_t<uint32_t, true, RUNS>(a, ent, a.cb_cursor, a.spill, fold)) return rc;
     }
-    if (int rc = launch_scatter_t<uint32_t, true>(a, ent, part, a.spill)) return rc;
+    if (int rc = launch_scatter_t<uint32_t, true, RUNS>(a, ent, part, a.spill)) return rc;
     if (a.num_cb) {
       hipLaunchKernelGGL(k_old_cb_bounds, dim3((a.num_cb + 255) / 256), dim3(256), 0, (hipStream_t)a.stream, a.plans,
                          a.cb_filter, a.num_cb, a.old32, a.old_tot, a.fp_size, a.lis, a.ob_lo, a.ob_n, a.cb_count);
@@ -4530,7 +4578,7 @@ extern "C" int rf_launch_build(const LaunchArgs* pa) {
     CHECK_LAUNCH();
     REC(EV_B_SCAN);
     REC(EV_B_SCATTER);
-    if (int rc = launch_sort_t<uint32_t, true, true>(a, ent, part, a.spill)) return rc;
+    if (int rc = launch_sort_t<uint32_t, true, true, RUNS>(a, ent, part, a.spill)) return rc;
   } else if (a.wide) {
     // incremental add: 64-bit entries; old entries first (decoded by rf_launch_old_decode)
     uint64_t* ent = (uint64_t*)a.ent;
@@ -4540,23 +4588,23 @@ extern "C" int rf_launch_build(const LaunchArgs* pa) {
                          a.old_tile_filter, a.old_tile_start, a.fp_size, ent, a.cb_count);
       CHECK_LAUNCH();
     }
-    if (a.num_tiles) { int rc = launch_hash_count_t<uint64_t>(a, ent, a.cb_count, nullptr, CountFold{}); if (rc) return rc; }
+    if (a.num_tiles) { int rc = launch_hash_count_t<uint64_t, true, RUNS>(a, ent, a.cb_count, nullptr, CountFold{}); if (rc) return rc; }
     REC(EV_B_HASH);
     hipLaunchKernelGGL(k_cb_scan, dim3(a.num_filters), dim3(256), 0, (hipStream_t)a.stream, a.plans, a.cb_count,
                        a.cb_count, a.cb_start, a.cb_cursor, nullptr);
     CHECK_LAUNCH();
     REC(EV_B_SCAN);
-    if (int rc = launch_scatter_t<uint64_t>(a, ent, part, nullptr)) return rc;
+    if (int rc = launch_scatter_t<uint64_t, true, RUNS>(a, ent, part, nullptr)) return rc;
     REC(EV_B_SCATTER);
-    if (int rc = launch_sort_t<uint64_t>(a, ent, part, nullptr)) return rc;
+    if (int rc = launch_sort_t<uint64_t, true, false, RUNS>(a, ent, part, nullptr)) return rc;
   } else {
     // fresh build: fused hash + partition into fixed regions (cb_count = fills)
     uint32_t* ent = (uint32_t*)a.ent;
     uint32_t* part = (uint32_t*)a.part;
     if (a.num_tiles) {
-#define L(K) hipLaunchKernelGGL((k_hash_scatter<K>), dim3(a.num_tiles), dim3(SCAT_NT), 0, (hipStream_t)a.stream, \
+#define L(K) hipLaunchKernelGGL((k_hash_scatter<K, false, RUNS>), dim3(a.num_tiles), dim3(SCAT_NT), 0, (hipStream_t)a.stream, \
                                 a.plans, a.tile_filter, a.tile_start, a.in0, a.offs, a.key_len, a.fp_size, a.seed, \
-                                part, a.cb_count, a.spill)
+                                part, a.cb_count, a.spill, runs)
       KIND_SWITCH(a.kind, L);
 #undef L
       CHECK_LAUNCH();
@@ -4569,12 +4617,12 @@ extern "C" int rf_launch_build(const LaunchArgs* pa) {
     if (a.num_tiles) {
       const CountFold fold{a.zero_outs ? (uint32_t*)a.outs : nullptr, (uint32_t)(sizeof(FilterOut) / 4) * a.num_filters,
                            a.spill + 1, a.cb_count, a.cb_start, a.num_filters};
-      if (int rc = launch_hash_count_t<uint32_t>(a, ent, a.cb_cursor, a.spill, fold)) return rc;
+      if (int rc = launch_hash_count_t<uint32_t, false, RUNS>(a, ent, a.cb_cursor, a.spill, fold)) return rc;
     }
     REC(EV_B_SCAN);
-    if (int rc = launch_scatter_t<uint32_t>(a, ent, part, a.spill)) return rc;
+    if (int rc = launch_scatter_t<uint32_t, false, RUNS>(a, ent, part, a.spill)) return rc;
     REC(EV_B_SCATTER);
-    if (int rc = launch_sort_t<uint32_t>(a, ent, part, a.spill)) return rc;
+    if (int rc = launch_sort_t<uint32_t, false, false, RUNS>(a, ent, part, a.spill)) return rc;
   }
   // the build's counters left zero for the next build (a.self_clean: fresh builds)
   const BuildClean clean = a.self_clean ? BuildClean{a.cb_count, a.cb_cursor, a.overflow, a.spill}
@@ -4601,6 +4649,10 @@ extern "C" int rf_launch_build(const LaunchArgs* pa) {
     if (int rc = launch_plines_list(a)) return rc;
   REC(EV_B_ASSEMBLE);
   return 0;
+}
+
+extern "C" int rf_launch_build(const LaunchArgs* pa) {
+  return pa->tile_value ? launch_build_t<true>(*pa) : launch_build_t<false>(*pa);
 }
 
 extern "C" int rf_launch_plines(const LaunchArgs* pa) {

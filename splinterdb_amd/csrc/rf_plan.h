@@ -47,7 +47,8 @@ struct FilterPlan {
   uint32_t num_new;    // new fingerprints
   uint32_t old_region; // entry slots reserved for decoded old entries (old num_fingerprints)
   uint32_t num_fp;     // routing_filter.num_fingerprints (new + old)
-  uint32_t value;
+  uint32_t value;      // of the new entries (chained batches: of the last run's; the others'
+                       // travel with the tiles, LaunchArgs::tile_value)
   uint32_t vs, rem, rvs, lnb;
   uint32_t num_indices;
   uint32_t cbits, bbits;  // coarse-bucket bits, bucket-in-coarse-bucket bits (sum = lnb)
@@ -58,7 +59,10 @@ struct FilterPlan {
   uint32_t lg_line, line_base;
   uint32_t lines_asm;  // 1: K6 cuts this filter's lines from its LDS page images; 0: k_plines
   // old filter (incremental add)
-  uint32_t old_num_indices, old_vs, old_rvs, npo;  // npo = new indices per old index
+  // npo = new indices per index of the filter the last routing_filter_add step started from
+  // (the old filter; in a chained batch, that filter plus every run but the last): the group
+  // width of the num_unique put-back quirk, its only use
+  uint32_t old_num_indices, old_vs, old_rvs, npo;
   uint32_t old_idx_base;  // first of this filter's old indices in the batch's old-index list
   uint32_t lines_flag;    // lines_asm, but a page's group table may not fit K6's LDS: such pages
                           // are flagged in pg_noline and k_plines cuts their indices' lines
@@ -179,6 +183,10 @@ struct LaunchArgs {
   const uint32_t* tile_filter;
   const uint32_t* tile_start;
   uint32_t num_tiles;
+  // chained batches (several runs of new inputs per filter): per tile, its run's value and
+  // end -- tiles are cut at run boundaries (nullptr: one run per filter, FilterPlan::value)
+  const uint32_t* tile_value;
+  const uint32_t* tile_end;
   const uint32_t* old_tile_filter;
   const uint32_t* old_tile_start;
   uint32_t num_old_tiles;

@@ -56,6 +56,7 @@ EXPORTED = [
     "rf_amd_batch_device_bytes", "rf_amd_batch_trim", "rf_amd_batch_stage_begin", "rf_amd_batch_stage_build",
     "rf_amd_batch_stage_abort", "rf_amd_lookup_server_error", "rf_amd_lookup_server_failed",
     "rf_amd_lookup_server_set_times", "rf_amd_diag_lookup_server_kill", "rf_amd_diag_lookup_ring",
+    "rf_amd_batch_create_runs", "rf_amd_filter_add_runs",
 ]
 ROUTE_MAX_WORLD = 16
 ASYNC_STATUS_RUNNING = 0  # src/platform_linux/async.h:137-140
@@ -124,6 +125,8 @@ def load_library(build_if_missing=True):
     L.rf_amd_engine_destroy.restype = None
     L.rf_amd_batch_create.argtypes = [vp, ctypes.POINTER(RfConfig), u32, vp, vp, vp, vp,
                                       ctypes.POINTER(vp)]
+    L.rf_amd_batch_create_runs.argtypes = [vp, ctypes.POINTER(RfConfig), u32, vp, vp, vp, vp, vp,
+                                           ctypes.POINTER(vp)]
     L.rf_amd_batch_destroy.argtypes = [vp]
     L.rf_amd_batch_destroy.restype = None
     L.rf_amd_batch_build_keys.argtypes = [vp, vp, u32, vp]
@@ -161,6 +164,8 @@ def load_library(build_if_missing=True):
     L.rf_amd_batch_num_filters.restype = u32
     L.rf_amd_filter_add.argtypes = [vp, ctypes.POINTER(RfConfig), ctypes.POINTER(RfImage),
                                     ctypes.POINTER(RfImage), vp, u64, ctypes.c_uint16]
+    L.rf_amd_filter_add_runs.argtypes = [vp, ctypes.POINTER(RfConfig), ctypes.POINTER(RfImage),
+                                         ctypes.POINTER(RfImage), vp, vp, vp, u32]
     L.rf_amd_filter_lookup_hashes.argtypes = [vp, ctypes.POINTER(RfConfig),
                                               ctypes.POINTER(RfImage), vp, u64, vp]
     L.rf_amd_filter_lookup_keys.argtypes = [vp, ctypes.POINTER(RfConfig), ctypes.POINTER(RfImage),
@@ -336,6 +341,42 @@ def routing_filter_add(cfg: RoutingConfig, old_filter, new_fp_arr, value=0, engi
         L.rf_amd_image_free(ctypes.byref(out))
     return RoutingFilter(info.num_fingerprints, info.num_unique, info.value_size,
                          info.num_indices, info.num_pages, pages, slots)
+
+
+def _image_out(L, cfg, out):
+    """an rf_amd_image the library allocated, copied into a RoutingFilter and freed"""
+    try:
+        info = out.info
+        npg = info.num_pages * cfg.page_size
+        pages = np.ctypeslib.as_array(out.pages, shape=(npg,)).copy()
+        slots = np.ctypeslib.as_array(out.slots, shape=(info.num_indices,)).copy()
+    finally:
+        L.rf_amd_image_free(ctypes.byref(out))
+    return RoutingFilter(info.num_fingerprints, info.num_unique, info.value_size,
+                         info.num_indices, info.num_pages, pages, slots)
+
+
+def routing_filter_add_runs(cfg: RoutingConfig, old_filter, fp_arrs, values, engine=None):
+    """A chain of routing_filter_add calls in one build (rf_amd_filter_add_runs): run j adds the
+    32-bit key hashes fp_arrs[j] with values[j] (strictly increasing) onto the result of run
+    j - 1, run 0 onto old_filter (or None). Returns the chain's last filter -- the one
+    maplet_compaction_task (src/trunk.c:3815-3868) keeps."""
+    eng = engine or default_engine()
+    L = load_library()
+    fps = [np.ascontiguousarray(a, dtype=np.uint32) for a in fp_arrs]
+    k = len(fps)
+    ptrs = (ctypes.c_void_p * max(1, k))(*[(a.ctypes.data if a.size else None) for a in fps])
+    lens = np.ascontiguousarray([a.size for a in fps], dtype=np.uint64)
+    vals = np.ascontiguousarray(values, dtype=np.uint16)
+    if vals.size != k:
+        raise PlatformStatusError(STATUS_BAD_PARAM, "one value per run")
+    out = RfImage()
+    old_c = old_filter._c() if old_filter is not None else None
+    _check(L.rf_amd_filter_add_runs(eng.h, ctypes.byref(cfg.c()),
+                                    ctypes.byref(old_c) if old_c is not None else None,
+                                    ctypes.byref(out), ctypes.cast(ptrs, ctypes.c_void_p), lens.ctypes.data,
+                                    vals.ctypes.data, k))
+    return _image_out(L, cfg, out)
 
 
 def routing_filter_lookup_hashes(cfg: RoutingConfig, filt, hashes, engine=None):
@@ -624,6 +665,35 @@ class FilterBatch:
                                      oi_arr.ctypes.data if oi_arr is not None else None,
                                      ctypes.byref(h)))
         self.h = h
+
+    @classmethod
+    def chained(cls, cfg: RoutingConfig, runs, old=None, engine=None):
+        """A chained batch (rf_amd_batch_create_runs): filter f is the end of the chain of
+        routing_filter_add calls runs[f] = [(count, value), ...] (values strictly increasing),
+        onto old[f] = (batch, i) or None, built in one build. The build calls take the inputs
+        concatenated filter-major, run-minor."""
+        self = cls.__new__(cls)
+        self.engine = engine or default_engine()
+        self.cfg = cfg
+        self.F = len(runs)
+        nr = np.ascontiguousarray([len(r) for r in runs], dtype=np.uint32)
+        rl = np.ascontiguousarray([c for r in runs for c, _ in r], dtype=np.uint32)
+        rv = np.ascontiguousarray([v for r in runs for _, v in r], dtype=np.uint16)
+        self.num_new = np.array([sum(c for c, _ in r) for r in runs], dtype=np.uint32)
+        self.values = np.array([(r[-1][1] if len(r) else 0) for r in runs], dtype=np.uint16)
+        self._keep = [nr, rl, rv]
+        ob_arr = oi_arr = None
+        if old is not None:
+            ob_arr = (ctypes.c_void_p * self.F)(*[(o[0].h.value if o else None) for o in old])
+            oi_arr = np.ascontiguousarray([(o[1] if o else 0) for o in old], dtype=np.uint32)
+            self._keep += [ob_arr, oi_arr, [o[0] for o in old if o]]
+        h = ctypes.c_void_p()
+        _check(load_library().rf_amd_batch_create_runs(
+            self.engine.h, ctypes.byref(cfg.c()), self.F, nr.ctypes.data, rl.ctypes.data, rv.ctypes.data,
+            ctypes.cast(ob_arr, ctypes.c_void_p) if ob_arr is not None else None,
+            oi_arr.ctypes.data if oi_arr is not None else None, ctypes.byref(h)))
+        self.h = h
+        return self
 
     @classmethod
     def imported(cls, cfg: RoutingConfig, infos, d_pages, d_slots, device_resident=True, engine=None):
