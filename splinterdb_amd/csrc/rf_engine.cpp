@@ -1,10 +1,10 @@
 // rf_engine.cpp -- host runtime of the MI355X routing-filter engine (C ABI: include/rf_amd.h).
 //
-// Owns device workspaces, builds the per-batch plan (geometry of src/routing_filter.c:
-// 357-389 per filter, plus the coarse-bucket / page-bound bookkeeping of this engine) and
-// issues the kernel sequence of rf_kernels.hip on one HIP stream. No compute happens on
-// the host: there is no CPU fallback, and every entry point fails with ENODEV when no HIP
-// device is present.
+// Owns device workspaces, gives each batch the buffers its plan asks for (the plan itself --
+// geometry of src/routing_filter.c:357-389 per filter, plus the coarse-bucket / page-bound
+// bookkeeping of this engine -- is rf_batch_plan.h's, host-only) and issues the kernel
+// sequence of rf_kernels.hip on one HIP stream. No compute happens on the host: there is no
+// CPU fallback, and every entry point fails with ENODEV when no HIP device is present.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <math.h>
@@ -17,6 +17,7 @@
 
 #include <map>
 #include <atomic>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -24,6 +25,7 @@
 #include "../../include/rf_amd.h"
 #include "../../include/rf_amd_diag.h"
 #include "rf_plan.h"
+#include "rf_batch_plan.h"
 
 using namespace rf;
 
@@ -289,41 +291,29 @@ struct DevBuf {
   T* as() const { return static_cast<T*>(p); }
 };
 
-struct rf_amd_batch {
+// every device buffer of a batch, named once: the members and bufs() (what destroy_on, trim and
+// device_bytes walk) both come from this list
+#define RF_BATCH_DEVBUFS(X)                                                                        \
+  X(d_runs) X(d_wave_tab) /* probe run bounds (rf_amd_batch_probe_*_runs), their wave table */     \
+  X(d_plans) X(d_outs) X(d_ent) X(d_part) X(d_sorted) X(d_cb_count) X(d_cb_start) X(d_cb_cursor)   \
+  X(d_cb_filter) X(d_overflow) X(d_idx_cnt) X(d_idx_start) X(d_slots) X(d_page_first)              \
+  X(d_pg_filter) X(d_pages) X(d_tile_filter) X(d_tile_start) X(d_old_tile_filter)                  \
+  X(d_old_tile_start) X(d_old_cnt) X(d_old_pos) X(d_first_old) X(d_has_old) X(d_pplans) X(d_lines) \
+  X(d_idx_filter) X(d_spill) X(d_old_idx_filter) X(d_old32) X(d_old_tot) X(d_ob_lo) X(d_ob_n)      \
+  X(d_pg_noline) X(d_pre) X(d_cb_out) X(d_lay_wg) X(d_lay_hand)                                    \
+  X(d_tile_value) X(d_tile_end) /* chained batches: each tile's run value and end */
+
+// a batch is its plan (rf_batch_plan.h: geometry, totals, maps) plus the device buffers that
+// plan asks for and the state of its builds
+struct rf_amd_batch : BatchPlan {
   rf_amd_engine* eng = nullptr;
   rf_amd_config cfg{};
-  uint32_t F = 0;
-  bool wide = false;
-  bool flag32 = false;      // wide build with 32-bit flagged entries (every fp_size + vs <= 31)
-  uint64_t old_total = 0;   // flag32: decoded old entries reserved (sum of old num_fingerprints)
-  std::vector<FilterPlan> plans;
-  // per-filter prefix arrays (F + 1 each) of the batch's per-element maps: tiles, old tiles,
-  // coarse buckets, pages, indices, decoded old indices. The maps themselves (element ->
-  // filter, tile -> first key) are filled on the device (k_seg_fill), so creating a batch
-  // uploads O(filters) bytes, not O(indices + pages)
-  enum { PRE_TILE, PRE_OTILE, PRE_CB, PRE_PG, PRE_IDX, PRE_OIDX, NUM_PRE };
-  std::vector<uint32_t> pre;  // NUM_PRE x (F + 1)
-  uint32_t* pre_of(int k) { return pre.data() + (size_t)k * (F + 1); }
-  uint32_t num_tiles = 0, num_old_tiles = 0, num_old_idx = 0;
-  bool chained = false;  // several runs of new inputs per filter (rf_amd_batch_create_runs)
-  DevBuf d_pre;
-  uint64_t E = 0, keys_total = 0;
-  uint32_t CB = 0, I = 0, PS = 0, PF = 0;
-  uint64_t NL = 0;         // probe lines (64 B each)
-  bool plines_needed = false;  // some filter's lines come from k_plines
-  uint32_t line_lmax = 0;  // max probe lines per index
-  DevBuf d_runs, d_wave_tab;        // probe run bounds (rf_amd_batch_probe_*_runs), their wave table
-  std::vector<uint64_t> runs_host;  // their last uploaded value
-  DevBuf d_plans, d_outs, d_ent, d_part, d_sorted, d_cb_count, d_cb_start, d_cb_cursor, d_cb_filter,
-      d_overflow, d_idx_cnt, d_idx_start, d_slots, d_page_first, d_pg_filter, d_pages, d_tile_filter,
-      d_tile_start, d_old_tile_filter, d_old_tile_start, d_old_cnt, d_old_pos, d_first_old, d_has_old, d_pplans, d_lines, d_idx_filter, d_spill,
-      d_old_idx_filter, d_old32, d_old_tot, d_ob_lo, d_ob_n, d_pg_noline, d_cb_out, d_lay_wg, d_lay_hand,
-      d_tile_value, d_tile_end;  // chained batches: each tile's run value and end
-  // K5 over several workgroups per filter (layout_groups): indices per workgroup, the grid of
-  // k_layout_seg (0: no filter is split), whether any filter keeps one workgroup, and the
-  // sequence number that tags a build's hand-offs (never 0: the words start out zero)
-  uint32_t lay_seg = 0, lay_grid = 0, lay_seq = 0;
-  bool lay_whole = true;
+#define X(name) DevBuf name;
+  RF_BATCH_DEVBUFS(X)
+#undef X
+  std::vector<uint64_t> runs_host;  // d_runs' last uploaded value
+  // the sequence number that tags a build's K5 hand-offs (never 0: the words start out zero)
+  uint32_t lay_seq = 0;
   bool counters_clean = false;  // the last build ran to its end and left the per-build counters zero (do_build)
   bool built = false;
   bool has_entries = false;  // built here: its sorted entries (d_part / d_sorted) are current
@@ -339,24 +329,32 @@ struct rf_amd_batch {
     for (auto ev : events) (void)hipEventDestroy(ev);
   }
   std::vector<DevBuf*> bufs() {
-    return {&d_runs, &d_wave_tab, &d_plans, &d_outs, &d_ent, &d_part, &d_sorted, &d_cb_count, &d_cb_start, &d_cb_cursor,
-            &d_cb_filter, &d_overflow, &d_idx_cnt, &d_idx_start, &d_slots, &d_page_first, &d_pg_filter,
-            &d_pages, &d_tile_filter, &d_tile_start, &d_old_tile_filter, &d_old_tile_start, &d_old_cnt,
-            &d_old_pos, &d_first_old, &d_has_old, &d_pplans, &d_lines, &d_idx_filter, &d_spill,
-            &d_old_idx_filter, &d_old32, &d_old_tot, &d_ob_lo, &d_ob_n, &d_pg_noline, &d_pre, &d_cb_out,
-            &d_lay_wg, &d_lay_hand, &d_tile_value, &d_tile_end};
+    return {
+#define X(name) &name,
+        RF_BATCH_DEVBUFS(X)
+#undef X
+    };
   }
 };
 
+// The environment switches of batch planning, read at every create and import (tests set them
+// between batches of one process).
 // RF_AMD_LAYOUT_SEG: indices per K5 workgroup, a power of two in [256, 4096] (default 4096;
 // larger values mean 4096, 0 or anything else the one-workgroup kernel for every filter).
-// Read when a batch is created.
-static uint32_t layout_seg_env() {
-  const char* e = getenv("RF_AMD_LAYOUT_SEG");
-  if (!e || !*e) return LAYOUT_SEG_MAX;
-  const unsigned long v = strtoul(e, nullptr, 10);
-  if (v < LAYOUT_SEG_MIN || (v & (v - 1))) return 0;
-  return v > LAYOUT_SEG_MAX ? LAYOUT_SEG_MAX : (uint32_t)v;
+// RF_AMD_LINE_SIGMA: line_log_group's margin (tuning knob, default 3.5).
+// RF_AMD_WIDE64, RF_AMD_OLD_DECODE, RF_AMD_OLD_RESPLIT_OFF (set at all): incremental adds keep
+// 64-bit entries / always decode old filters' images / decode them when the geometry changed.
+static PlanKnobs plan_knobs_env() {
+  PlanKnobs k;
+  k.wide64 = getenv("RF_AMD_WIDE64") != nullptr;
+  k.old_decode = getenv("RF_AMD_OLD_DECODE") != nullptr;
+  k.old_resplit_off = getenv("RF_AMD_OLD_RESPLIT_OFF") != nullptr;
+  if (const char* e = getenv("RF_AMD_LAYOUT_SEG"); e && *e) {
+    const unsigned long v = strtoul(e, nullptr, 10);
+    k.layout_seg = (v < LAYOUT_SEG_MIN || (v & (v - 1))) ? 0 : v > LAYOUT_SEG_MAX ? LAYOUT_SEG_MAX : (uint32_t)v;
+  }
+  if (const char* e = getenv("RF_AMD_LINE_SIGMA"); e && atof(e) > 0.0) k.line_sigma = atof(e);
+  return k;
 }
 
 extern "C" const char* rf_amd_last_error(void) { return g_err.c_str(); }
@@ -462,316 +460,44 @@ static void engine_destroy_now(rf_amd_engine* e, bool device_sync) {
 }
 
 static int check_cfg(const rf_amd_config* cfg) {
-  if (!cfg) return fail(RF_AMD_EINVAL, "null config");
-  if (cfg->page_size != MAX_PAGE || cfg->pages_per_extent != 32)
-    return fail(RF_AMD_EINVAL, "engine supports 4 KiB pages in 32-page extents");
-  if (cfg->fingerprint_size == 0 || cfg->fingerprint_size > 32 || cfg->log_index_size > MAX_LIS ||
-      cfg->log_index_size < 3)
-    return fail(RF_AMD_EINVAL, "unsupported fingerprint_size / log_index_size");
+  std::string msg;
+  if (int rc = check_config(cfg, &msg)) return fail(rc, msg);
   return 0;
 }
 
-static uint32_t vsize_of(uint32_t value) { return value == 0 ? 0 : 32 - __builtin_clz(value); }
-
-// Probe-line group size (k_plines): the largest G = 2^g <= min(IS, 64) whose 64-byte line
-// (128 encoding bits for n + G, 384 remainder bits for n * rvs) holds mean + SIGMA sd + 2
-// entries, n ~ Poisson(lam*G) with lam = fingerprints per bucket (< 2 by the choice of
-// log_num_buckets). Larger G = smaller line table but more overflowed lines (those probes
-// walk the image). SIGMA: RF_AMD_LINE_SIGMA (tuning knob), default 3.5 (lam is an upper
-// bound; table size measured not to matter for the probe, overflow rate does).
-// Returns g + 1, or 0 = no lines (rvs > 32: probes walk the image).
-// K6 cuts a filter's probe lines from its LDS page images when the per-page group table
-// fits: each block needs IS/G + 1 entries. Returns 0: never (k_plines cuts every line),
-// 1: always (even a page of the smallest blocks fits), 2: page by page -- K6 flags a page
-// whose blocks do not fit and k_plines cuts those pages' lines.
-static int lines_in_assembly(uint32_t lis, uint32_t lg_line, uint32_t page_size) {
-  const uint32_t IS = 1u << lis, L = IS >> (lg_line - 1);
-  const uint32_t min_block = 2 + (IS - 1) / 8 + 4 + 3;
-  const uint32_t maxb = page_size / min_block + 1;
-  if (maxb > ASM_MAXB_HOST || L + 1 > ASM_GT_HOST) return 0;
-  return (uint64_t)maxb * (L + 1) <= ASM_GT_HOST ? 1 : 2;
+// what the planner needs to know of the old filters a batch names (empty: none)
+static std::vector<OldFilter> old_filters_of(const rf_amd_engine* e, uint32_t F, rf_amd_batch* const* old_batch,
+                                             const uint32_t* old_index) {
+  std::vector<OldFilter> olds;
+  if (!old_batch) return olds;
+  olds.resize(F);
+  for (uint32_t f = 0; f < F; f++) {
+    const rf_amd_batch* ob = old_batch[f];
+    if (!ob) continue;
+    const uint32_t oi = old_index ? old_index[f] : 0;
+    OldFilter& o = olds[f];
+    o.present = true;
+    o.plan = oi < ob->F ? &ob->plans[oi] : nullptr;
+    o.fingerprint_size = ob->cfg.fingerprint_size;
+    o.log_index_size = ob->cfg.log_index_size;
+    o.has_entries = ob->has_entries;
+    o.wide = ob->wide;
+    o.built = ob->built;
+    o.same_device = ob->eng->device == e->device;
+  }
+  return olds;
 }
 
-static double line_sigma() {
-  const char* e = getenv("RF_AMD_LINE_SIGMA");
-  const double v = e ? atof(e) : 0.0;
-  return v > 0.0 ? v : 3.5;
-}
-static uint32_t line_log_group(uint32_t lis, uint32_t rvs, double lam) {
-  if (rvs > 32) return 0;
-  const double sg = line_sigma();
-  for (int g = (int)(lis < 6 ? lis : 6); g >= 0; g--) {
-    const double G = (double)(1u << g), mean = lam * G;
-    const double cap = rvs ? std::min(128.0 - G, 384.0 / rvs) : 128.0 - G;
-    if (mean + sg * sqrt(mean) + 2.0 <= cap) return (uint32_t)g + 1;
-  }
-  return 0;
-}
-
-// num_indices of a filter of nfp fingerprints (src/routing_filter.c:374-379)
-static uint32_t num_indices_of(uint64_t nfp, uint32_t lis) {
-  uint32_t lnb = 63 - __builtin_clzll(nfp);
-  if (lnb < lis) lnb = lis;
-  return 1u << (lnb - lis);
-}
-
-// rf_amd_batch_create, and rf_amd_batch_create_runs with num_runs != nullptr: filter f's new
-// inputs are then num_runs[f] runs (run_len / run_value, filter-major) and num_new / value are
-// not read. nothing is allocated or launched before the arguments have been checked.
-static int batch_create(rf_amd_engine* e, const rf_amd_config* cfg, uint32_t num_filters,
-                        const uint32_t* num_new, const uint16_t* value, const uint32_t* num_runs,
-                        const uint32_t* run_len, const uint16_t* run_value,
-                        rf_amd_batch* const* old_batch, const uint32_t* old_index, rf_amd_batch** out) {
-  if (!e) return fail(RF_AMD_ENODEV, "no engine");
-  if (int rc = check_cfg(cfg)) return rc;
-  if (num_filters == 0 || !(num_runs ? (run_len && run_value) : num_new != nullptr) || !out)
-    return fail(RF_AMD_EINVAL, "empty batch");
-  std::vector<uint32_t> run_first(num_filters + 1, 0u), run_total;  // chained: first run, inputs per filter
-  if (num_runs) {
-    run_total.assign(num_filters, 0u);
-    for (uint32_t f = 0; f < num_filters; f++) {
-      if (num_runs[f] == 0) return fail(RF_AMD_EINVAL, "a filter without runs");
-      run_first[f + 1] = run_first[f] + num_runs[f];
-      uint64_t tot = 0;
-      for (uint32_t r = run_first[f]; r < run_first[f + 1]; r++) {
-        if (run_len[r] == 0) return fail(RF_AMD_EINVAL, "zero-length run");
-        if (r > run_first[f] && run_value[r] <= run_value[r - 1])
-          return fail(RF_AMD_EINVAL, "run values of a filter must be strictly increasing");
-        tot += run_len[r];
-      }
-      if (tot > rf_amd_max_fingerprints(cfg))
-        return fail(RF_AMD_EINVAL, "num_fingerprints over routing_filter_max_fingerprints (reference: UB)");
-      if (cfg->fingerprint_size + vsize_of(run_value[run_first[f + 1] - 1]) > 32)
-        return fail(RF_AMD_EINVAL, "fp_size + value_size > 32");
-      const rf_amd_batch* ob = (old_batch && old_batch[f]) ? old_batch[f] : nullptr;
-      const uint32_t oi = old_index ? old_index[f] : 0;
-      if (ob && oi < ob->F && vsize_of(run_value[run_first[f]]) < ob->plans[oi].vs)
-        return fail(RF_AMD_EINVAL, "first run's value narrower than the old filter's value_size");
-      run_total[f] = (uint32_t)tot;
-    }
-    num_new = run_total.data();
-  }
-  HIPCHK(hipSetDevice(e->device));
-  auto* b = new rf_amd_batch();
-  b->eng = e;
-  b->cfg = *cfg;
-  b->F = num_filters;
-  b->chained = num_runs != nullptr;
-  b->plans.resize(num_filters);
-  b->pre.assign((size_t)rf_amd_batch::NUM_PRE * (num_filters + 1), 0u);
-  const uint32_t lis = cfg->log_index_size, fps = cfg->fingerprint_size, P = cfg->page_size;
-  const uint32_t IS = 1u << lis;
-  uint64_t e_first = 0, key_first = 0;
-  uint32_t cb_base = 0, idx_base = 0, page_base = 0, pf_base = 0;
-  uint64_t line_base = 0;
-  std::vector<std::pair<const rf_amd_batch*, const FilterPlan*>> olds(num_filters, {nullptr, nullptr});
-  for (uint32_t f = 0; f < num_filters; f++) {
-    FilterPlan& p = b->plans[f];
-    memset(&p, 0, sizeof(p));
-    const rf_amd_batch* ob = (old_batch && old_batch[f]) ? old_batch[f] : nullptr;
-    const FilterPlan* op = nullptr;
-    if (ob) {
-      const uint32_t oi = old_index ? old_index[f] : 0;
-      if (oi >= ob->F || !ob->built || ob->eng->device != e->device) {
-        delete b;
-        return fail(RF_AMD_EINVAL, "bad old filter reference");
-      }
-      op = &ob->plans[oi];
-      b->wide = true;
-    }
-    const uint32_t v = num_runs ? run_value[run_first[f + 1] - 1] : value ? value[f] : 0;
-    p.num_new = num_new[f];
-    p.old_region = op ? op->num_fp : 0;
-    const uint64_t nfp = (uint64_t)p.num_new + p.old_region;
-    if (nfp > rf_amd_max_fingerprints(cfg)) {  // checked before the u32 descriptor field can wrap
-      delete b;
-      return fail(RF_AMD_EINVAL, "num_fingerprints over routing_filter_max_fingerprints (reference: UB)");
-    }
-    p.num_fp = (uint32_t)nfp;
-    if (p.num_fp == 0) {
-      delete b;
-      return fail(RF_AMD_EINVAL, "routing_filter_add with zero fingerprints (reference: UB)");
-    }
-    uint32_t lnb = 31 - __builtin_clz(p.num_fp);
-    if (lnb < lis) lnb = lis;
-    p.vs = vsize_of(v);
-    if (lnb > fps || (1u << (lnb - lis)) > MAX_INDICES || fps + p.vs > 32 || (op && p.vs < op->vs)) {
-      delete b;
-      return fail(RF_AMD_EINVAL, "filter geometry out of range (over routing_filter_max_fingerprints, "
-                                 "fp_size + value_size > 32, or value narrower than old filter)");
-    }
-    p.lnb = lnb;
-    p.value = v;
-    p.rem = fps - lnb;
-    p.rvs = p.rem + p.vs;
-    p.num_indices = 1u << (lnb - lis);
-    int cb = (int)lnb - (int)CB_LOG_MEAN;
-    if (cb < 0) cb = 0;
-    if (cb > (int)(lnb - lis)) cb = (int)(lnb - lis);
-    // load factor ~1 (nfp just over a power of two: C3/C4's 2^20 keys) leaves coarse buckets
-    // of 2^12 buckets half full (~4K of SORT_CAP entries), and K4's cost is mostly per
-    // workgroup: use coarse buckets of 2^13 buckets (~8K entries, still >= 9 sd under
-    // SORT_CAP) with K4 bins of two buckets each (at most MAX_BINS bins, MAX_IPC indices)
-    p.binsh = 0;
-    if (cb >= 1 && lnb - cb == CB_LOG_MEAN && lis + 9 >= CB_LOG_MEAN + 1 /* ipc <= MAX_IPC */ &&
-        nfp * 1000 <= (1026ull << lnb)) {
-      cb -= 1;
-      p.binsh = 1;
-    }
-    p.cbits = (uint32_t)cb;
-    p.bbits = lnb - p.cbits;
-    p.e_first = e_first;
-    p.key_first = key_first;
-    p.cb_base = cb_base;
-    p.idx_base = idx_base;
-    // page bound: sum of block sizes <= NI*(12 + IS/8) + E*(1+rvs)/8; next-fit <= 2x + 1
-    const uint64_t bound = (uint64_t)p.num_indices * (12 + IS / 8) + (nfp * (1 + p.rvs) + 7) / 8;
-    uint64_t cap = 2 * ((bound + P - 1) / P) + 2;
-    if (cap > p.num_indices) cap = p.num_indices;
-    p.page_cap = (uint32_t)cap;
-    p.page_base = page_base;
-    p.pf_base = pf_base;
-    p.lg_line = line_log_group(lis, p.rvs, (double)nfp / (double)(1ull << lnb));
-    p.line_base = (uint32_t)line_base;
-    const int la = p.lg_line ? lines_in_assembly(lis, p.lg_line, P) : 0;
-    p.lines_asm = la != 0;
-    p.lines_flag = la == 2;
-    if (p.lg_line && la != 1) b->plines_needed = true;
-    if (p.lg_line) {
-      line_base += (uint64_t)p.num_indices << (lis - (p.lg_line - 1));
-      b->line_lmax = std::max(b->line_lmax, IS >> (p.lg_line - 1));
-    }
-    if (op) {
-      p.old_num_indices = op->num_indices;
-      p.old_vs = op->vs;
-      p.old_rvs = op->rvs;
-      p.npo = p.num_indices / op->num_indices;
-      p.old_pages = ob->d_pages.as<uint8_t>() + (uint64_t)op->page_base * P;
-      p.old_slots = ob->d_slots.as<uint64_t>() + op->idx_base;
-      olds[f] = {ob, op};
-    }
-    uint32_t ntiles = (p.num_new + TILE_KEYS - 1) / TILE_KEYS;
-    if (num_runs) {
-      // the last chain step's group width (num_unique quirk): from the filter that step starts
-      // from -- the old filter plus every run but the last; tiles end at run boundaries
-      const uint64_t prev_fp = nfp - run_len[run_first[f + 1] - 1];
-      p.npo = prev_fp ? p.num_indices / num_indices_of(prev_fp, lis) : 1u;
-      ntiles = 0;
-      for (uint32_t r = run_first[f]; r < run_first[f + 1]; r++) ntiles += (run_len[r] + TILE_KEYS - 1) / TILE_KEYS;
-    }
-    {
-      auto pre = [&](int k, uint32_t count) { b->pre_of(k)[f + 1] = b->pre_of(k)[f] + count; };
-      pre(rf_amd_batch::PRE_TILE, ntiles);
-      pre(rf_amd_batch::PRE_OTILE, (p.old_region + TILE_KEYS - 1) / TILE_KEYS);
-      pre(rf_amd_batch::PRE_CB, 1u << p.cbits);
-      pre(rf_amd_batch::PRE_PG, p.page_cap);
-      pre(rf_amd_batch::PRE_IDX, p.num_indices);
-    }
-    e_first += nfp;
-    key_first += p.num_new;
-    cb_base += 1u << p.cbits;
-    idx_base += p.num_indices;
-    page_base += p.page_cap;
-    pf_base += p.page_cap + 1;
-  }
-  if (b->wide) {
-    // 32-bit entries when (e << 1) | flag fits: fp_size + value_size <= 31 in every filter
-    b->flag32 = getenv("RF_AMD_WIDE64") == nullptr;
-    for (const auto& p : b->plans) b->flag32 = b->flag32 && fps + p.vs <= 31;
-  }
-  if (!b->wide || b->flag32) {
-    // fresh and 32-bit incremental builds: the fused kernel partitions the new keys straight
-    // into SORT_CAP slots per coarse bucket (k_hash_scatter), so each filter's entry region is
-    // its buckets' regions (>= its num_fingerprints: incremental builds' sorted entries, laid
-    // out by the scan of new + old counts, fit in it too)
-    e_first = 0;
-    for (auto& p : b->plans) {
-      p.e_first = e_first;
-      e_first += (uint64_t)CB_REGION << p.cbits;
-    }
-  }
-  if (b->wide) {
-    // old filters: read in place from their batch's sorted entries when the geometry is the
-    // same (32-bit pipeline; the old batch built here, not imported), else decoded from the
-    // image -- only those join the batch's old-index list and old32
-    const bool direct_ok = b->flag32 && getenv("RF_AMD_OLD_DECODE") == nullptr;
-    for (uint32_t f = 0; f < num_filters; f++) {
-      const rf_amd_batch* ob = olds[f].first;
-      const FilterPlan* op = olds[f].second;
-      if (!op) continue;
-      FilterPlan& p = b->plans[f];
-      // in place also across a geometry change (lnb grew: rounds 2, 3 and 5 of the compaction
-      // chain), as long as each new coarse bucket lies inside one old one (cbits did not shrink)
-      // (RF_AMD_OLD_RESPLIT_OFF: decode those, for A/B)
-      const bool same_cfg = direct_ok && ob->has_entries && ob->cfg.fingerprint_size == fps &&
-                            ob->cfg.log_index_size == lis;
-      const bool same_geo = op->lnb == p.lnb && op->cbits == p.cbits;
-      const bool resplit = p.cbits >= op->cbits && p.lnb >= op->lnb && getenv("RF_AMD_OLD_RESPLIT_OFF") == nullptr;
-      if (same_cfg && (same_geo || resplit)) {
-        const uint32_t* es = ob->wide ? ob->d_sorted.as<uint32_t>() : ob->d_part.as<uint32_t>();
-        p.old_direct = 1;
-        p.old_cbits = op->cbits;
-        p.old_bbits = op->bbits;
-        p.old_entries = es + op->e_first;
-        p.old_idx_start = ob->d_idx_start.as<uint32_t>() + op->idx_base;
-        p.old_idx_cnt = ob->d_idx_cnt.as<uint32_t>() + op->idx_base;
-        continue;
-      }
-      p.old_idx_base = b->num_old_idx;
-      p.old_first = b->old_total;
-      b->old_total += p.old_region;
-      b->num_old_idx += op->num_indices;
-    }
-    // decoded old indices per filter (0 for filters without an old filter or read in place)
-    uint32_t* po = b->pre_of(rf_amd_batch::PRE_OIDX);
-    for (uint32_t f = 0; f < num_filters; f++) {
-      const FilterPlan& p = b->plans[f];
-      po[f + 1] = po[f] + ((olds[f].second && !p.old_direct) ? p.old_num_indices : 0u);
-    }
-  }
-  // K5 workgroups: the G segments of a split filter go to one XCD (workgroup w runs on XCD
-  // w % 8), consecutive there, so segment q - 1 is workgroup w - 8: dispatched before its waiter
-  std::vector<uint32_t> lay_wg;
-  b->lay_seg = layout_seg_env();
-  if (P > MAX_PAGE || num_filters >= (1u << 26)) b->lay_seg = 0;
-  {
-    uint32_t pos[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    b->lay_whole = false;
-    for (uint32_t f = 0; f < num_filters; f++) {
-      const uint32_t G = layout_groups(b->plans[f], b->lay_seg);
-      if (G == 1) {
-        b->lay_whole = true;
-        continue;
-      }
-      const uint32_t x = (uint32_t)(std::min_element(pos, pos + 8) - pos);
-      const uint32_t w0 = x + 8 * pos[x];
-      const size_t need = w0 + 8 * (size_t)(G - 1) + 1;
-      if (lay_wg.size() < need) lay_wg.resize(need, ~0u);
-      for (uint32_t q = 0; q < G; q++) lay_wg[w0 + 8 * q] = f << 6 | q;
-      pos[x] += G;
-    }
-    b->lay_grid = (uint32_t)lay_wg.size();
-  }
-  b->num_tiles = b->pre_of(rf_amd_batch::PRE_TILE)[num_filters];
-  b->num_old_tiles = b->pre_of(rf_amd_batch::PRE_OTILE)[num_filters];
-  b->E = e_first;
-  b->keys_total = key_first;
-  b->CB = cb_base;
-  b->I = idx_base;
-  b->PS = page_base;
-  b->PF = pf_base;
-  if (line_base > 0xffffffffull) {
-    delete b;
-    return fail(RF_AMD_EINVAL, "batch too large (probe lines > 2^32)");
-  }
-  b->NL = line_base;
+// batch_create, step 2: the device buffers the plan asks for
+static int create_alloc(rf_amd_batch* b) {
   const size_t esz = (b->wide && !b->flag32) ? 8 : 4;
+  const uint32_t P = b->cfg.page_size;
   int rc = 0;
-  DevPool* pool = &e->pool;
+  DevPool* pool = &b->eng->pool;
   const uint64_t ta0 = pool_trace_ns();
-  rc |= b->d_plans.alloc(sizeof(FilterPlan) * num_filters, pool);
-  rc |= b->d_pplans.alloc(16ull * num_filters, pool);
-  rc |= b->d_outs.alloc(sizeof(FilterOut) * num_filters, pool);
+  rc |= b->d_plans.alloc(sizeof(FilterPlan) * b->F, pool);
+  rc |= b->d_pplans.alloc(16ull * b->F, pool);
+  rc |= b->d_outs.alloc(sizeof(FilterOut) * b->F, pool);
   rc |= b->d_ent.alloc(esz * b->E + 64, pool);
   rc |= b->d_part.alloc(esz * b->E + 64, pool);
   if (b->wide) rc |= b->d_sorted.alloc(4 * b->E + 64, pool);
@@ -820,17 +546,37 @@ static int batch_create(rf_amd_engine* e, const rf_amd_config* cfg, uint32_t num
     }
   }
   pool_trace("create allocs", 0, ta0);
-  if (rc) {
-    delete b;
-    return fail(RF_AMD_ENOMEM, "device allocation failed");
+  return rc ? fail(RF_AMD_ENOMEM, "device allocation failed") : 0;
+}
+
+// batch_create, step 3a: where each filter's old filter lies on the device -- its image, and
+// for those read in place (old_direct) its batch's sorted entries with their index runs
+static void fill_old_pointers(rf_amd_batch* b, rf_amd_batch* const* old_batch, const uint32_t* old_index) {
+  for (uint32_t f = 0; old_batch && f < b->F; f++) {
+    const rf_amd_batch* ob = old_batch[f];
+    if (!ob) continue;
+    const FilterPlan* op = &ob->plans[old_index ? old_index[f] : 0];
+    FilterPlan& p = b->plans[f];
+    p.old_pages = ob->d_pages.as<uint8_t>() + (uint64_t)op->page_base * b->cfg.page_size;
+    p.old_slots = ob->d_slots.as<uint64_t>() + op->idx_base;
+    if (!p.old_direct) continue;
+    const uint32_t* es = ob->wide ? ob->d_sorted.as<uint32_t>() : ob->d_part.as<uint32_t>();
+    p.old_entries = es + op->e_first;
+    p.old_idx_start = ob->d_idx_start.as<uint32_t>() + op->idx_base;
+    p.old_idx_cnt = ob->d_idx_cnt.as<uint32_t>() + op->idx_base;
   }
-  hipStream_t st = e->stream;
+}
+
+// batch_create, steps 3b and 4: uploads, map fills, and the wait for them (the batch's host
+// vectors may change once it is handed out). On failure work may still be queued.
+static int create_enqueue(rf_amd_batch* b) {
+  hipStream_t st = b->eng->stream;
   // Page bytes the reference never writes are zero on a fresh cache page (SURVEY finding 4).
   // K6 writes every byte of every page it assembles (block bytes and the zero tail), and no
   // reader looks past a filter's num_pages, so the reserved pages a build does not use are
   // not cleared (page_cap reserves ~2x the pages: clearing them cost a compaction round
   // ~0.3 ms); only the tail pad that windowed reads of the last page may touch is zeroed.
-  HIPCHK(hipMemsetAsync(b->d_pages.as<uint8_t>() + (size_t)b->PS * P, 0, 256, st));
+  HIPCHK(hipMemsetAsync(b->d_pages.as<uint8_t>() + (size_t)b->PS * b->cfg.page_size, 0, 256, st));
   if (const char* pz = getenv("RF_AMD_POISON")) {
     // test hook: fill every work buffer -- the page images included -- with a pattern, so
     // that a kernel reading memory it did not write in this build, or leaving page bytes
@@ -844,66 +590,82 @@ static int batch_create(rf_amd_engine* e, const rf_amd_config* cfg, uint32_t num
 #define UP(buf, vec) \
   if (!(vec).empty()) HIPCHK(hipMemcpyAsync(buf.p, (vec).data(), sizeof((vec)[0]) * (vec).size(), hipMemcpyHostToDevice, st))
   UP(b->d_plans, b->plans);
-  std::vector<uint4> pp(num_filters);
-  for (uint32_t f = 0; f < num_filters; f++) {
-    const FilterPlan& q = b->plans[f];
-    pp[f] = make_uint4(q.vs | (q.rem << 8) | (q.rvs << 16) | (q.lg_line << 24), q.line_base, q.idx_base, 0);
-  }
-  UP(b->d_pplans, pp);
+  UP(b->d_pplans, b->pplans);
   UP(b->d_pre, b->pre);
-  UP(b->d_lay_wg, lay_wg);
-  // tile maps of a chained batch, built here: tiles are cut at run boundaries and carry their
-  // run's value and end (both relative to the filter's first input, like tile_start)
-  std::vector<uint32_t> tf, ts, tv, te;
-  if (b->chained) {
-    for (std::vector<uint32_t>* v : {&tf, &ts, &tv, &te}) v->reserve(b->num_tiles);
-    for (uint32_t f = 0; f < num_filters; f++) {
-      uint32_t first = 0;
-      for (uint32_t r = run_first[f]; r < run_first[f + 1]; r++) {
-        const uint32_t end = first + run_len[r];
-        for (uint32_t s0 = first; s0 < end; s0 += TILE_KEYS) {
-          tf.push_back(f);
-          ts.push_back(s0);
-          tv.push_back(run_value[r]);
-          te.push_back(std::min(end, s0 + (uint32_t)TILE_KEYS));
-        }
-        first = end;
-      }
-    }
-    UP(b->d_tile_filter, tf);
-    UP(b->d_tile_start, ts);
-    UP(b->d_tile_value, tv);
-    UP(b->d_tile_end, te);
-  }
+  UP(b->d_lay_wg, b->lay_wg);
+  UP(b->d_tile_filter, b->tile_filter);  // the tile maps of a chained batch
+  UP(b->d_tile_start, b->tile_start);
+  UP(b->d_tile_value, b->tile_value);
+  UP(b->d_tile_end, b->tile_end);
 #undef UP
   // hand-off tags start out zero, once per batch: a build's tag is never 0
   if (b->lay_grid) HIPCHK(hipMemsetAsync(b->d_lay_hand.p, 0, 16ull * b->lay_grid, st));
   {
     // element -> filter maps (and tile -> first key) from the prefix arrays, on the device
-    const uint32_t F1 = num_filters + 1;
+    const uint32_t F1 = b->F + 1;
     const uint32_t* dp = b->d_pre.as<uint32_t>();
     struct M { int k; DevBuf* fof; DevBuf* start; };
-    const M maps[] = {{rf_amd_batch::PRE_TILE, &b->d_tile_filter, &b->d_tile_start},
-                      {rf_amd_batch::PRE_OTILE, &b->d_old_tile_filter, &b->d_old_tile_start},
-                      {rf_amd_batch::PRE_CB, &b->d_cb_filter, nullptr},
-                      {rf_amd_batch::PRE_PG, &b->d_pg_filter, nullptr},
-                      {rf_amd_batch::PRE_IDX, &b->d_idx_filter, nullptr},
-                      {rf_amd_batch::PRE_OIDX, &b->d_old_idx_filter, nullptr}};
+    const M maps[] = {{PRE_TILE, &b->d_tile_filter, &b->d_tile_start},
+                      {PRE_OTILE, &b->d_old_tile_filter, &b->d_old_tile_start},
+                      {PRE_CB, &b->d_cb_filter, nullptr},
+                      {PRE_PG, &b->d_pg_filter, nullptr},
+                      {PRE_IDX, &b->d_idx_filter, nullptr},
+                      {PRE_OIDX, &b->d_old_idx_filter, nullptr}};
     for (const M& m : maps) {
-      const uint32_t n = b->pre_of(m.k)[num_filters];
+      const uint32_t n = b->pre_of(m.k)[b->F];
       if (n == 0 || !m.fof->p) continue;
-      if (b->chained && m.k == rf_amd_batch::PRE_TILE) continue;  // uploaded above
-      if (rf_launch_seg_fill(st, dp + (size_t)m.k * F1, num_filters, n, m.fof->as<uint32_t>(),
-                             m.start ? m.start->as<uint32_t>() : nullptr, TILE_KEYS)) {
-        delete b;
+      if (b->chained && m.k == PRE_TILE) continue;  // uploaded above
+      if (rf_launch_seg_fill(st, dp + (size_t)m.k * F1, b->F, n, m.fof->as<uint32_t>(),
+                             m.start ? m.start->as<uint32_t>() : nullptr, TILE_KEYS))
         return fail(RF_AMD_EINVAL, "map fill launch failed");
-      }
     }
   }
   const uint64_t ts0 = pool_trace_ns();
   HIPCHK(hipStreamSynchronize(st));
   pool_trace("create sync", 0, ts0);
-  *out = b;
+  return 0;
+}
+
+// rf_amd_batch_create, and rf_amd_batch_create_runs with num_runs != nullptr: filter f's new
+// inputs are then num_runs[f] runs (run_len / run_value, filter-major) and num_new / value are
+// not read. Four steps: check and plan (rf_batch_plan.h; nothing is allocated or launched
+// before the arguments have been checked), allocate, fill in pointers and upload, launch and
+// synchronise.
+static int batch_create(rf_amd_engine* e, const rf_amd_config* cfg, uint32_t num_filters,
+                        const uint32_t* num_new, const uint16_t* value, const uint32_t* num_runs,
+                        const uint32_t* run_len, const uint16_t* run_value,
+                        rf_amd_batch* const* old_batch, const uint32_t* old_index, rf_amd_batch** out) {
+  if (!e) return fail(RF_AMD_ENODEV, "no engine");
+  if (int rc = check_cfg(cfg)) return rc;
+  if (num_filters == 0 || !(num_runs ? (run_len && run_value) : num_new != nullptr) || !out)
+    return fail(RF_AMD_EINVAL, "empty batch");
+  const std::vector<OldFilter> olds = old_filters_of(e, num_filters, old_batch, old_index);
+  BatchInput in;
+  in.cfg = cfg;
+  in.num_filters = num_filters;
+  in.num_new = num_new;
+  in.value = value;
+  in.num_runs = num_runs;
+  in.run_len = run_len;
+  in.run_value = run_value;
+  in.olds = olds.empty() ? nullptr : olds.data();
+  auto b = std::make_unique<rf_amd_batch>();
+  std::string msg;
+  if (int rc = plan_batch(in, plan_knobs_env(), b.get(), &msg)) return fail(rc, msg);
+  b->eng = e;
+  b->cfg = *cfg;
+
+  HIPCHK(hipSetDevice(e->device));
+  if (int rc = create_alloc(b.get())) return rc;
+
+  fill_old_pointers(b.get(), old_batch, old_index);
+  if (int rc = create_enqueue(b.get())) {
+    // queued work may still read the batch's host vectors and write the blocks that go back
+    // to the pool with it
+    (void)hipStreamSynchronize(e->stream);
+    return rc;
+  }
+  *out = b.release();
   return 0;
 }
 
@@ -919,14 +681,7 @@ extern "C" int rf_amd_batch_create_runs(rf_amd_engine* e, const rf_amd_config* c
                                         const uint16_t* run_value, rf_amd_batch* const* old_batch,
                                         const uint32_t* old_index, rf_amd_batch** out) {
   if (!num_runs || !run_len || !run_value) return fail(RF_AMD_EINVAL, "null run arrays");
-  // one run per filter: exactly rf_amd_batch_create (runs and filters then share their index)
-  bool single = true;
-  for (uint32_t f = 0; f < num_filters && single; f++) single = num_runs[f] == 1;
-  if (single) {
-    for (uint32_t f = 0; f < num_filters; f++)
-      if (run_len[f] == 0) return fail(RF_AMD_EINVAL, "zero-length run");
-    return batch_create(e, cfg, num_filters, run_len, run_value, nullptr, nullptr, nullptr, old_batch, old_index, out);
-  }
+  // (one run per filter: the planner makes that exactly rf_amd_batch_create's batch)
   return batch_create(e, cfg, num_filters, nullptr, nullptr, num_runs, run_len, run_value, old_batch, old_index, out);
 }
 
@@ -1508,7 +1263,7 @@ static int batch_errors(rf_amd_batch* b) {
 static ProbeGroup probe_group_of(const rf_amd_batch* b, uint32_t f) {
   const FilterPlan& p = b->plans[f];
   ProbeGroup g;
-  g.x = p.vs | (p.rem << 8) | (p.rvs << 16) | (p.lg_line << 24);
+  g.x = pplan_word(p);
   g.err = b->err_host[f];
   g.fpl = b->cfg.fingerprint_size | (b->cfg.log_index_size << 8);
   g.pad = 0;
@@ -2551,99 +2306,67 @@ extern "C" int rf_amd_batch_image_ptrs(rf_amd_batch* b, uint32_t f, void** d_pag
 // Filter f's pages are the num_pages[f] * page_size bytes after those of filters < f in
 // `pages`, its index slots (relocatable, filter-relative) the num_indices[f] u64 after
 // those of filters < f in `slots`. Probe lines are cut from the images by k_plines.
+// batch_import, steps 3b and 4: uploads, the probe lines' kernel, and the wait for them. On
+// failure work may still be queued (reading outs / idx_filter, the caller's host vectors).
+static int import_enqueue(rf_amd_batch* b, const std::vector<FilterOut>& outs, const std::vector<uint32_t>& idx_filter,
+                          const void* pages, const uint64_t* slots, hipMemcpyKind kind) {
+  const uint32_t F = b->F;
+  const size_t page_bytes = (size_t)b->PS * b->cfg.page_size;
+  hipStream_t st = b->eng->stream;
+  HIPCHK(hipMemcpyAsync(b->d_outs.p, outs.data(), sizeof(FilterOut) * F, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemsetAsync(b->d_pages.as<uint8_t>() + page_bytes, 0, 256, st));
+  HIPCHK(hipMemcpyAsync(b->d_pages.p, pages, page_bytes, kind, st));
+  HIPCHK(hipMemcpyAsync(b->d_slots.p, slots, 8ull * b->I, kind, st));
+  HIPCHK(hipMemcpyAsync(b->d_idx_filter.p, idx_filter.data(), 4ull * b->I, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(b->d_plans.p, b->plans.data(), sizeof(FilterPlan) * F, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(b->d_pplans.p, b->pplans.data(), 16ull * F, hipMemcpyHostToDevice, st));
+  {
+    LaunchArgs a = make_args(b, st);
+    if (int lrc = rf_launch_plines(&a))
+      return fail(RF_AMD_EINVAL, std::string("probe-line launch: ") + hipGetErrorString((hipError_t)lrc));
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  return note_built(b, st);
+}
+
+// Four steps, as batch_create: check and plan (rf_batch_plan.h), allocate, upload, launch and
+// synchronise.
 static int batch_import(rf_amd_engine* e, const rf_amd_config* cfg, uint32_t F, const rf_amd_filter_info* infos,
                         const void* pages, const uint64_t* slots, hipMemcpyKind kind, rf_amd_batch** out) {
   if (int rc = check_cfg(cfg)) return rc;
   if (F == 0 || !infos || !pages || !slots) return fail(RF_AMD_EINVAL, "bad image");
-  HIPCHK(hipSetDevice(e->device));
-  auto* b = new rf_amd_batch();
+  auto b = std::make_unique<rf_amd_batch>();
+  std::string msg;
+  if (int rc = plan_import(cfg, F, infos, plan_knobs_env(), b.get(), &msg)) return fail(rc, msg);
   b->eng = e;
   b->cfg = *cfg;
-  b->F = F;
-  b->plans.resize(F);
-  const uint32_t lis = cfg->log_index_size;
-  std::vector<uint4> pp(F);
-  std::vector<uint32_t> idx_filter;
-  uint64_t pages_total = 0, idx_total = 0, lines_total = 0;
-  for (uint32_t f = 0; f < F; f++) {
-    const rf_amd_filter_info& in = infos[f];
-    FilterPlan& p = b->plans[f];
-    memset(&p, 0, sizeof(p));
-    uint32_t lnb = in.num_fingerprints ? 31 - __builtin_clz(in.num_fingerprints) : 0;
-    if (lnb < lis) lnb = lis;
-    if (in.num_fingerprints == 0 || lnb > cfg->fingerprint_size || (1u << (lnb - lis)) > MAX_INDICES ||
-        in.num_indices != (1u << (lnb - lis)) || in.value_size > 32 - cfg->fingerprint_size || in.error ||
-        in.num_pages == 0) {
-      delete b;
-      return fail(RF_AMD_EINVAL, "image geometry out of range (filter " + std::to_string(f) + ")");
-    }
-    p.num_fp = in.num_fingerprints;
-    p.lnb = lnb;
-    p.vs = in.value_size;
-    p.rem = cfg->fingerprint_size - lnb;
-    p.rvs = p.rem + p.vs;
-    p.num_indices = in.num_indices;
-    p.page_cap = in.num_pages;
-    p.page_base = (uint32_t)pages_total;
-    p.idx_base = (uint32_t)idx_total;
-    p.lg_line = line_log_group(lis, p.rvs, (double)in.num_fingerprints / (double)(1ull << lnb));
-    p.line_base = (uint32_t)lines_total;
-    pp[f] = make_uint4(p.vs | (p.rem << 8) | (p.rvs << 16) | (p.lg_line << 24), p.line_base, p.idx_base, 0);
-    if (p.lg_line) {
-      lines_total += (uint64_t)p.num_indices << (lis - (p.lg_line - 1));
-      b->line_lmax = std::max(b->line_lmax, (1u << lis) >> (p.lg_line - 1));
-      b->plines_needed = true;
-    }
-    idx_filter.insert(idx_filter.end(), p.num_indices, f);
-    pages_total += in.num_pages;
-    idx_total += p.num_indices;
-  }
-  if (lines_total >= (1ull << 32) || pages_total >= (1ull << 32)) {
-    delete b;
-    return fail(RF_AMD_EINVAL, "import too large");
-  }
-  b->PS = (uint32_t)pages_total;
-  b->I = (uint32_t)idx_total;
-  b->NL = lines_total;
-  const size_t page_bytes = (size_t)pages_total * cfg->page_size;
+
+  HIPCHK(hipSetDevice(e->device));
   DevPool* pool = &e->pool;
   int rc = b->d_plans.alloc(sizeof(FilterPlan) * F, pool);
   rc |= b->d_pplans.alloc(16ull * F, pool);
-  rc |= b->d_pages.alloc(page_bytes + 256, pool);
-  rc |= b->d_slots.alloc(8ull * idx_total, pool);
+  rc |= b->d_pages.alloc((size_t)b->PS * cfg->page_size + 256, pool);
+  rc |= b->d_slots.alloc(8ull * b->I, pool);
   rc |= b->d_lines.alloc(64ull * b->NL + 64, pool);
-  rc |= b->d_idx_filter.alloc(4ull * idx_total, pool);
+  rc |= b->d_idx_filter.alloc(4ull * b->I, pool);
   rc |= b->d_outs.alloc(sizeof(FilterOut) * F, pool);
-  if (rc) {
-    delete b;
-    return fail(RF_AMD_ENOMEM, "device allocation failed");
-  }
+  if (rc) return fail(RF_AMD_ENOMEM, "device allocation failed");
+
   std::vector<FilterOut> outs(F);
-  for (uint32_t f = 0; f < F; f++) outs[f] = FilterOut{infos[f].num_unique, infos[f].num_pages, 0u, 0u};
-  hipStream_t st = e->stream;
-  HIPCHK(hipMemcpyAsync(b->d_outs.p, outs.data(), sizeof(FilterOut) * F, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemsetAsync(b->d_pages.as<uint8_t>() + page_bytes, 0, 256, st));
-  HIPCHK(hipMemcpyAsync(b->d_pages.p, pages, page_bytes, kind, st));
-  HIPCHK(hipMemcpyAsync(b->d_slots.p, slots, 8ull * idx_total, kind, st));
-  HIPCHK(hipMemcpyAsync(b->d_idx_filter.p, idx_filter.data(), 4ull * idx_total, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(b->d_plans.p, b->plans.data(), sizeof(FilterPlan) * F, hipMemcpyHostToDevice, st));
-  HIPCHK(hipMemcpyAsync(b->d_pplans.p, pp.data(), 16ull * F, hipMemcpyHostToDevice, st));
-  {
-    LaunchArgs a = make_args(b, st);
-    if (int lrc = rf_launch_plines(&a)) {
-      delete b;
-      return fail(RF_AMD_EINVAL, std::string("probe-line launch: ") + hipGetErrorString((hipError_t)lrc));
-    }
+  std::vector<uint32_t> idx_filter;
+  idx_filter.reserve(b->I);
+  for (uint32_t f = 0; f < F; f++) {
+    outs[f] = FilterOut{infos[f].num_unique, infos[f].num_pages, 0u, 0u};
+    idx_filter.insert(idx_filter.end(), b->plans[f].num_indices, f);
   }
-  HIPCHK(hipStreamSynchronize(st));  // host vectors above are released on return
-  if (int erc = note_built(b, st)) {
-    delete b;
+  if (int erc = import_enqueue(b.get(), outs, idx_filter, pages, slots, kind)) {
+    (void)hipStreamSynchronize(e->stream);  // queued copies may still read the vectors above
     return erc;
   }
-  b->err_host.assign(F, 0u);  // imports carry no error bits (checked above)
+  b->err_host.assign(F, 0u);  // imports carry no error bits (checked by the planner)
   b->err_ready.store(true, std::memory_order_release);
   b->built = true;
-  *out = b;
+  *out = b.release();
   return 0;
 }
 
@@ -2826,8 +2549,7 @@ extern "C" void rf_amd_image_free(rf_amd_image* img) {
 }
 
 extern "C" uint64_t rf_amd_max_fingerprints(const rf_amd_config* cfg) {
-  const uint64_t addrs_per_extent = (uint64_t)cfg->page_size * cfg->pages_per_extent / 8;
-  return 2ull * addrs_per_extent * (1ull << cfg->log_index_size) - 1;
+  return max_fingerprints(*cfg);
 }
 
 // src/routing_filter.c:1119-1139 as the reference's release build evaluates it (-O3

@@ -2299,10 +2299,9 @@ __device__ __forceinline__ void assemble_atomic(const FilterPlan& P, uint32_t p,
   }
 }
 
-constexpr uint32_t ASM_MAXB = 128;  // blocks per page held in LDS (more: assemble_atomic)
+// (ASM_MAXB, ASM_GT: rf_plan.h -- the host plans with them)
 constexpr uint32_t ASM_RUN = 16;    // entries per thread-run in phase C
 constexpr uint32_t ASM_MAXE = 16384;  // entries per page covered by the run table
-constexpr uint32_t ASM_GT = 1024;     // group-start table entries per page (lines_asm bound)
 
 // 64 bits of the LDS page image from bit `bitpos` (the image has 4 words of tail padding)
 __device__ __forceinline__ uint64_t lds_bits64(const uint32_t* s_pg, uint32_t bitpos) {

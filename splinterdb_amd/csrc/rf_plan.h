@@ -32,8 +32,9 @@ constexpr int BIG_NT = 1024;
 constexpr int BIG_GRID = 64;
 constexpr int LAYOUT_NT = 1024;
 constexpr int ASM_NT = 128;
-constexpr uint32_t ASM_MAXB_HOST = 128;  // = ASM_MAXB in rf_kernels.hip (blocks per page in LDS)
-constexpr uint32_t ASM_GT_HOST = 1024;   // = ASM_GT (group-start table entries per page)
+// K6 (k_assemble) LDS tables, which the host's lines_in_assembly bounds a filter's pages by
+constexpr uint32_t ASM_MAXB = 128;  // blocks per page held in LDS (more: assemble_atomic)
+constexpr uint32_t ASM_GT = 1024;   // group-start table entries per page (lines_asm bound)
 
 enum InputKind { IN_KEYS24 = 0, IN_KEYS_W = 1, IN_KEYS_B = 2, IN_VAR = 3, IN_HASH = 4, IN_PAIR = 5 };
 
