@@ -58,6 +58,12 @@ int rf_amd_diag_lookup_ring(rf_amd_engine *e);
  * rf_amd_lookup_server_failed) */
 int rf_amd_diag_lookup_server_kill(rf_amd_engine *e, int err, uint32_t gap_us);
 
+/* how many builds of this process ran K4 as the bitmap kernel (k_cb_bitmap: fresh single-run
+ * batches whose every filter has an in-bucket key of at most 16 bits, unless
+ * RF_AMD_K4_BITMAP=0) instead of the bucket sort: a test reads it before and after a build to
+ * see which of the two the build took */
+uint64_t rf_amd_diag_k4_bitmap_builds(void);
+
 /* the source id the library was built from (16 hex digits of SHA-256 over the engine's
  * sources and headers, splinterdb_amd/build.py source_id): the Python loader refuses a
  * library whose id differs from the tree's (a stale prebuilt .so) */

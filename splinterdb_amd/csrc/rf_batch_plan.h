@@ -126,6 +126,7 @@ struct BatchPlan {
   uint32_t lay_seg = 0, lay_grid = 0;
   bool lay_whole = true;
   std::vector<uint32_t> lay_wg;
+  bool k4_bitmap = false;  // K4 runs k_cb_bitmap, not k_cb_sort (k4_bitmap_batch)
   // tile maps of a chained batch: tiles are cut at run boundaries and carry their run's value
   // and end (both relative to the filter's first input, like tile_start)
   std::vector<uint32_t> tile_filter, tile_start, tile_value, tile_end;
@@ -270,6 +271,26 @@ inline void assign_layout(BatchPlan& b) {
     pos[x] += G;
   }
   b.lay_grid = (uint32_t)b.lay_wg.size();
+}
+
+// K4 by bitmap (k_cb_bitmap). The entries of one coarse bucket of a fresh build differ only in
+// their low bbits + rvs bits (the bits above are the bucket's number), so sorting and
+// deduplicating them is building a set of 2^(bbits + rvs) bits. A filter qualifies when that
+// set fits K4_BITMAP_MAX_BITS, an index owns whole 32-bit words of it (lis + rvs >= 5), and
+// the num_unique quirk cannot bite (an index's first entry is compared with UINT32_MAX >>
+// value_size, which a fingerprint equals only if fp_size + vs == 32).
+inline bool k4_bitmap_filter(const FilterPlan& p, const rf_amd_config& cfg) {
+  return p.bbits + p.rvs <= K4_BITMAP_MAX_BITS && cfg.log_index_size + p.rvs >= 5 &&
+         cfg.fingerprint_size + p.vs < 32;
+}
+// The batch takes the bitmap kernel only when every filter qualifies and the build is fresh and
+// single-run: old entries (wide, flag32) are never deduplicated, and the runs of a chained batch
+// carry different values.
+inline bool k4_bitmap_batch(const BatchPlan& b, const rf_amd_config& cfg) {
+  if (b.wide || b.flag32 || b.chained || b.plans.empty()) return false;
+  for (const FilterPlan& p : b.plans)
+    if (!k4_bitmap_filter(p, cfg)) return false;
+  return true;
 }
 
 // Old filters of an incremental batch: read in place from their batch's sorted entries when
@@ -420,6 +441,7 @@ inline int plan_batch(const BatchInput& in0, const PlanKnobs& knobs, BatchPlan* 
   b.lay_seg = knobs.layout_seg;
   if (cfg.page_size > MAX_PAGE || F >= (1u << 26)) b.lay_seg = 0;
   assign_layout(b);
+  b.k4_bitmap = k4_bitmap_batch(b, cfg);
   b.num_tiles = b.pre_of(PRE_TILE)[F];
   b.num_old_tiles = b.pre_of(PRE_OTILE)[F];
   if (b.NL > 0xffffffffull) return plan_fail(err, RF_AMD_EINVAL, "batch too large (probe lines > 2^32)");

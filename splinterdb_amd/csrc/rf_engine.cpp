@@ -1003,6 +1003,7 @@ static LaunchArgs make_args(rf_amd_batch* b, hipStream_t st) {
   a.lay_seq = b->lay_seq;
   a.lay_seg = b->lay_seg;
   a.lay_whole = b->lay_whole ? 1u : 0u;
+  a.k4_bitmap = b->k4_bitmap ? 1u : 0u;
   a.events = b->events.empty() ? nullptr : reinterpret_cast<void**>(b->events.data() + (size_t)b->ev_set * NUM_EVENTS);
   a.ev_mask = b->ev_mask;
   return a;
@@ -1895,6 +1896,9 @@ struct LookupClock {
 #define RF_AMD_SRC_ID "unknown"
 #endif
 extern "C" const char* rf_amd_build_id(void) { return RF_AMD_SRC_ID; }
+
+extern "C" uint64_t rf_k4_bitmap_builds(void);  // rf_kernels.hip: counted where K4 is launched
+extern "C" uint64_t rf_amd_diag_k4_bitmap_builds(void) { return rf_k4_bitmap_builds(); }
 
 extern "C" int rf_amd_diag_lookup_stats(uint64_t* out, int reset) {
   if (!out) return fail(RF_AMD_EINVAL, "null output");

@@ -11,6 +11,8 @@
 //                     counting sort by filter bucket, per-bucket insertion sort, dedupe
 //                     (src/routing_filter.c:471-482), per-index counts (:484-494),
 //                     num_unique (:572-574)
+//      k_cb_bitmap    K4 of fresh builds whose entries vary in at most 16 bits inside a coarse
+//                     bucket: a bit set in LDS instead of the sort, same outputs
 //   K4b k_cb_sort_big same for coarse buckets over LDS capacity (duplicate-heavy input)
 //   K5 k_layout       per filter: block sizes (:599-602) and the greedy page placement
 //                     (:603-610) as a parallel pointer-jumping scan; index slots (:612-620)
@@ -27,6 +29,8 @@
 // result depends only on the multiset of entries, exactly like the reference's sort.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <atomic>
 
 #include "rf_device.h"
 #include "rf_plan.h"
@@ -1089,6 +1093,122 @@ __global__ __launch_bounds__(SORT_NT, 6) void k_cb_sort(const FilterPlan* __rest
   DBG_PHASE(8);
   if constexpr (LIST) __syncthreads();  // the next bucket reuses the LDS
   }
+}
+
+// K4 by bitmap: fresh single-run builds whose entries vary, inside a coarse bucket, only in
+// their low kw = bbits + rvs <= K4_BITMAP_MAX_BITS bits (the bits above are the bucket's number
+// cbl; the host decides, k4_bitmap_batch). Sorting and deduplicating such a bucket is building
+// the set of its keys e & (2^kw - 1): one LDS atomicOr per entry into a bitmap of 2^kw bits, then
+// the set bits in ascending order are the kept entries. Thread t owns bitmap words [4t, 4t + 4)
+// (one 16-byte LDS access; a narrower key leaves the upper words, cleared like the rest, empty).
+// One block scan of the threads' popcounts gives every word's exclusive prefix, written back
+// over the bitmap: index l of the bucket owns words [l << wsh, (l + 1) << wsh), wsh = lis + rvs
+// - 5, so its start and count are two reads of those prefixes. All entries carry one value, so
+// kept entries have distinct fingerprints, none of them UINT32_MAX >> vs (fp_size + vs < 32):
+// the bucket adds `kept` to num_unique. No ranks, bins, sorting networks or dedupe pass.
+// Same inputs, outputs and grid as k_cb_sort<uint32_t, false, false, false, false>.
+__global__ __launch_bounds__(SORT_NT, 8) void k_cb_bitmap(const FilterPlan* __restrict__ plans,
+                                                          const uint32_t* __restrict__ cb_filter,
+                                                          const uint32_t* __restrict__ cb_count,
+                                                          const uint32_t* __restrict__ cb_start,
+                                                          const uint32_t* __restrict__ part,
+                                                          uint32_t* __restrict__ sorted32,
+                                                          uint32_t* __restrict__ idx_cnt,
+                                                          uint32_t* __restrict__ idx_start,
+                                                          FilterOut* __restrict__ outs,
+                                                          uint32_t* __restrict__ overflow, uint32_t lis,
+                                                          const uint32_t* __restrict__ spill) {
+  constexpr int PER = SORT_CAP / SORT_NT;
+  constexpr uint32_t BM_WORDS = (1u << K4_BITMAP_MAX_BITS) / 32;
+  static_assert(BM_WORDS == 4 * SORT_NT, "one 16-byte bitmap access per thread");
+  static_assert(K4_BITMAP_MAX_BITS <= 16 && SORT_CAP % 2 == 0, "16-bit keys, staged in pairs");
+  DBG_PHASE(15);
+  __shared__ __attribute__((aligned(16))) uint32_t s_bm[BM_WORDS];  // the set, then word prefixes
+  __shared__ __attribute__((aligned(16))) uint16_t s_key[SORT_CAP];  // kept keys in order
+  __shared__ uint32_t s_tmp[SORT_NT / WAVE + 1];
+  const uint32_t cb = xcd_chunk(blockIdx.x, gridDim.x);  // a filter's buckets share an XCD (its partition's L2)
+  const uint32_t f = cb_filter[cb];
+  const FilterPlan& P = plans[f];
+  const uint32_t n = cb_count[cb];
+  const uint32_t cbl = cb - P.cb_base;
+  // fused build without spill: fixed SORT_CAP regions; otherwise the scanned starts
+  const uint32_t cb_rel = (spill && *spill == 0) ? cbl * CB_REGION : cb_start[cb];
+  if (n > SORT_CAP) {  // handled by k_cb_sort_big
+    if (threadIdx.x == 0) overflow[1 + atomicAdd(&overflow[0], 1u)] = cb;
+    return;
+  }
+  const uint32_t kw = P.bbits + P.rvs, kmask = (1u << kw) - 1u;
+  // the bucket's entry loads go out first (clamped, branch-free) and land while the bitmap is
+  // cleared; the barrier after the clearing orders only LDS
+  uint32_t v[PER];
+  const uint32_t* src = part + P.e_first + cb_rel;
+  const uint32_t nm1 = n ? n - 1 : 0u;
+#pragma unroll
+  for (int k = 0; k < PER; k++) v[k] = src[min(threadIdx.x + k * SORT_NT, nm1)];
+  v4u* bm4 = reinterpret_cast<v4u*>(s_bm) + threadIdx.x;
+  *bm4 = v4u{0u, 0u, 0u, 0u};
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+  DBG_PHASE(0);
+#pragma unroll
+  for (int k = 0; k < PER; k++) {
+    if (threadIdx.x + k * SORT_NT < n) {
+      const uint32_t key = v[k] & kmask;
+      atomicOr(&s_bm[key >> 5], 1u << (key & 31u));
+    }
+  }
+  __syncthreads();
+  DBG_PHASE(1);
+  const v4u w = *bm4;
+  const uint32_t c0 = __popc(w.x), c1 = __popc(w.y), c2 = __popc(w.z), c3 = __popc(w.w);
+  uint32_t kept;
+  const uint32_t pos = block_excl_scan<SORT_NT>(c0 + c1 + c2 + c3, s_tmp, &kept);
+  DBG_PHASE(2);
+  // word prefixes over this thread's own words (no other thread reads them before the barrier)
+  *bm4 = v4u{pos, pos + c0, pos + c0 + c1, pos + c0 + c1 + c2};
+  {
+    uint32_t p = pos;
+    const uint32_t ww[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      uint32_t x = ww[j];
+      const uint32_t base = (threadIdx.x * 4u + j) << 5;
+      while (x) {
+        s_key[p++] = (uint16_t)(base + (uint32_t)__builtin_ctz(x));
+        x &= x - 1u;
+      }
+    }
+  }
+  __syncthreads();
+  DBG_PHASE(5);
+  // copy out: e = bucket number | key, two keys per LDS word and 8-byte stores where the
+  // bucket's first slot is even (always, unless the partition spilled)
+  const uint32_t hi = cbl << kw;
+  uint32_t* dst = sorted32 + P.e_first + cb_rel;
+  if (((P.e_first + cb_rel) & 1u) == 0) {
+    const uint32_t* k2 = reinterpret_cast<const uint32_t*>(s_key);
+    v2u* dst2 = reinterpret_cast<v2u*>(dst);
+    for (uint32_t i = threadIdx.x; i < kept / 2; i += SORT_NT) {
+      const uint32_t u = k2[i];
+      dst2[i] = v2u{hi | (u & 0xffffu), hi | (u >> 16)};
+    }
+    if ((kept & 1u) && threadIdx.x == 0) dst[kept - 1] = hi | s_key[kept - 1];
+  } else {
+    for (uint32_t i = threadIdx.x; i < kept; i += SORT_NT) dst[i] = hi | s_key[i];
+  }
+  DBG_PHASE(6);
+  const uint32_t ipc = 1u << (P.bbits - lis), wsh = lis + P.rvs - 5u;
+  const uint32_t idx0 = P.idx_base + (cbl << (P.bbits - lis));
+  for (uint32_t l = threadIdx.x; l < ipc; l += SORT_NT) {
+    const uint32_t w0 = l << wsh, w1 = (l + 1) << wsh;
+    const uint32_t lo = s_bm[w0], up = w1 < BM_WORDS ? s_bm[w1] : kept;
+    idx_cnt[idx0 + l] = up - lo;
+    idx_start[idx0 + l] = cb_rel + lo;
+  }
+  DBG_PHASE(7);
+  if (threadIdx.x == 0) atomicAdd(&outs[f].num_unique, kept);
+  DBG_PHASE(8);
 }
 
 // K4m: the bucket sort of 32-bit incremental builds (routing_filter_add with an old filter,
@@ -4499,12 +4619,35 @@ static bool k4m_enabled() {
   return v != 0;
 }
 
+// K4 by bitmap for the batches the planner marked (LaunchArgs::k4_bitmap); RF_AMD_K4_BITMAP=0:
+// the bucket sort instead, for A/B. g_k4_bitmap_builds counts the builds that took it
+// (rf_amd_diag_k4_bitmap_builds).
+static bool k4_bitmap_enabled() {
+  static int v = -1;
+  if (v < 0) {
+    const char* e = getenv("RF_AMD_K4_BITMAP");
+    v = (e && e[0] == '0') ? 0 : 1;
+  }
+  return v != 0;
+}
+static std::atomic<uint64_t> g_k4_bitmap_builds{0};
+extern "C" uint64_t rf_k4_bitmap_builds(void) { return g_k4_bitmap_builds.load(std::memory_order_relaxed); }
+
 template <typename EntT, bool FL = (sizeof(EntT) == 8), bool DUAL = false, bool RUNS = false>
 static int launch_sort_t(const LaunchArgs& a, EntT* ent, EntT* part, const uint32_t* spill) {
-  bool merged = false;
+  bool launched = false;
+  if constexpr (sizeof(EntT) == 4 && !FL && !DUAL && !RUNS) {
+    if (a.k4_bitmap && k4_bitmap_enabled()) {
+      launched = true;
+      hipLaunchKernelGGL(k_cb_bitmap, dim3(a.num_cb), dim3(SORT_NT), 0, (hipStream_t)a.stream, a.plans, a.cb_filter,
+                         a.cb_count, a.cb_start, part, a.sorted32, a.idx_cnt, a.idx_start, a.outs, a.overflow, a.lis,
+                         spill);
+      g_k4_bitmap_builds.fetch_add(1, std::memory_order_relaxed);
+    }
+  }
   if constexpr (DUAL) {
     if (k4m_enabled()) {
-      merged = true;
+      launched = true;
       hipLaunchKernelGGL((k_cb_merge<RUNS>), dim3(a.num_cb), dim3(SORT_NT), 0, (hipStream_t)a.stream, a.plans, a.cb_filter,
                        a.cb_count, a.cb_start, (const uint32_t*)part, a.old32, a.ob_lo, a.ob_n, a.sorted32, a.idx_cnt,
                        a.idx_start, a.outs, a.overflow, a.lis, a.first_old, a.has_old, spill, a.cb_outs);
@@ -4517,7 +4660,7 @@ static int launch_sort_t(const LaunchArgs& a, EntT* ent, EntT* part, const uint3
                          a.overflow);
     }
   }
-  if (!merged) {
+  if (!launched) {
     hipLaunchKernelGGL((k_cb_sort<EntT, FL, DUAL, false, RUNS>), dim3(a.num_cb), dim3(SORT_NT), 0, (hipStream_t)a.stream, a.plans,
                        a.cb_filter, a.cb_count, a.cb_start, part, a.old32, a.ob_lo, a.ob_n, a.sorted32, a.idx_cnt,
                        a.idx_start, a.outs, a.overflow, a.lis, a.first_old, a.has_old, spill, a.cb_outs, nullptr);

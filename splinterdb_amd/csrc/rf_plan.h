@@ -28,6 +28,9 @@ constexpr int SORT_CAP = 9216;   // entries per coarse bucket held in LDS (means
 #endif
 // fused build: each coarse bucket's region in `part` (SORT_CAP slots, spaced CB_REGION apart)
 constexpr uint32_t CB_REGION = SORT_CAP + RF_REGION_PAD;
+// K4 by bitmap (k_cb_bitmap): fresh builds whose entries differ, inside a coarse bucket, only in
+// their low bbits + rvs bits are sorted and deduplicated as a set of that many bits in LDS
+constexpr uint32_t K4_BITMAP_MAX_BITS = 16;  // 2^16 bits = 8 KiB, one 16-byte access per thread
 constexpr int BIG_NT = 1024;
 constexpr int BIG_GRID = 64;
 constexpr int LAYOUT_NT = 1024;
@@ -239,6 +242,7 @@ struct LaunchArgs {
   uint32_t lay_seq;
   uint32_t lay_seg;    // indices per layout workgroup (0: one workgroup per filter)
   uint32_t lay_whole;  // some filter of the batch is laid out by one workgroup
+  uint32_t k4_bitmap;  // every filter of the batch takes K4's bitmap kernel (BatchPlan::k4_bitmap)
   uint32_t self_clean;  // K5 leaves the build's counters zero: the next build skips k_build_init
   uint32_t zero_outs;   // no k_build_init ran before this build: it zeroes `outs` itself
   const uint64_t* probe_runs;  // probes grouped by filter: runs[f] <= i < runs[f+1] (nullptr: per-probe ids)

@@ -55,6 +55,10 @@ if KID == 1:
              9: "merge split (t0)", 10: "merge run (t0)", 5: "scan+compact", 6: "write out",
              7: "index bounds", 8: "uniq+end"}
     order = [15, 0, 1, 2, 3, 4, 9, 10, 5, 6, 7, 8]
+    if (ts[:, 3] == 0).all():  # k_cb_bitmap ran (RF_AMD_K4_BITMAP=0 brings the sort back)
+        names = {15: "entry", 0: "clear", 1: "load+set bits", 2: "popcount+scan", 5: "emit keys",
+                 6: "write out", 7: "index bounds", 8: "uniq+end"}
+        order = [15, 0, 1, 2, 5, 6, 7, 8]
 elif KID == 5:
     names = {15: "entry", 0: "new load", 1: "rank+DMA issue", 2: "bin scan", 3: "scatter", 4: "bin sort+old landed",
              5: "dedupe+compact", 6: "merge (split + run)", 7: "index bounds", 8: "uniq+end"}
