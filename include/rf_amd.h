@@ -164,6 +164,58 @@ int rf_amd_probe_filters_host(rf_amd_engine *e, rf_amd_batch *const *batches, co
 int rf_amd_probe_many_hashes_host(rf_amd_engine *e, rf_amd_batch *const *batches,
                                   const uint32_t *filter_index, const uint64_t *counts,
                                   uint32_t num_groups, const uint32_t *h_hashes, uint64_t *h_found);
+/* ---- multi-get: resident filter sets, fan-out probes, candidate lists -------------------
+ * The device form of the call above, for a multi-get that probes many keys, each against the
+ * maplets along its trunk path (trunk_merge_lookup, src/trunk.c:6008-6075, :6295-6330), from
+ * device pointers in one launch.
+ * A filter set is a resident table of num_members filters of any batches of engine e: member g
+ * is filter filter_index[g] (NULL: 0) of batches[g]; batches[g] == NULL is NULL_ROUTING_FILTER
+ * (finds nothing). Each member keeps its own batch's routing config (fingerprint_size and
+ * log_index_size may differ between members). Members are validated as rf_amd_probe_filters_host
+ * validates groups: an unbuilt batch, a batch of another engine or a bad filter index is EINVAL;
+ * a member whose build failed finds nothing. create waits for builds issued on the engine
+ * stream and allocates the set's device table (from the engine's pool); no later call on the
+ * set allocates or synchronises. The set holds pointers into its members' batches and no
+ * references: the batches must outlive the set's last probe (the rule of rf_amd_lookup_submit).
+ * rf_amd_batch_trim of a member leaves the set valid (pages, slots and probe lines keep their
+ * addresses). destroy synchronises the device, as rf_amd_batch_destroy does. */
+typedef struct rf_amd_filter_set rf_amd_filter_set;
+int  rf_amd_filter_set_create(rf_amd_engine *e, rf_amd_batch *const *batches,
+                              const uint32_t *filter_index, uint32_t num_members,
+                              rf_amd_filter_set **out);
+void rf_amd_filter_set_destroy(rf_amd_filter_set *s);
+uint32_t rf_amd_filter_set_num_members(const rf_amd_filter_set *s);
+/* fan-out probes: key i is looked up in the K members d_member[i*K .. i*K+K) (row-major; an
+ * id >= num_members finds nothing). d_member == NULL: K must equal num_members and slot j is
+ * member j. d_found[i*K + j] = routing_filter_lookup's found_values of key i in that member.
+ * Each key is read and hashed once. Asynchronous on stream (NULL = the engine's); all pointers
+ * are device memory; a build still in flight is ordered by the caller as for any
+ * device-pointer probe.
+ * The keys form takes the key lengths of rf_amd_batch_probe_keys (any key_len > 0) and hashes
+ * with the members' seed: EINVAL when the non-NULL members' seeds differ (the hashes form has no
+ * such restriction). EINVAL: K == 0, d_member == NULL with K != num_members, n * K >= 2^56, and
+ * -- unless n == 0, which is OK and touches nothing -- a NULL input or output. */
+int rf_amd_filter_set_probe_keys(rf_amd_filter_set *s, const void *d_keys, uint32_t key_len,
+                                 const uint32_t *d_member, uint32_t K, uint64_t n,
+                                 uint64_t *d_found, void *stream);
+int rf_amd_filter_set_probe_hashes(rf_amd_filter_set *s, const uint32_t *d_hashes,
+                                   const uint32_t *d_member, uint32_t K, uint64_t n,
+                                   uint64_t *d_found, void *stream);
+/* the set bits of m found_values words as an ordered candidate list: record =
+ * index << 8 | value, index ascending, and within one word value DESCENDING (the order in
+ * which routing_filter_get_next_value hands them out, src/routing_filter.h:94-105; with the
+ * fan-out's index = key * K + slot these are trunk_merge_lookup's (key, bundle, branch)
+ * candidates, src/trunk.c:6057-6060). *d_count = the total number of candidates (all of them,
+ * also when > cap); only the first cap records are written and nothing is written past
+ * d_cand[cap) (cap == 0: d_cand may be NULL). Works on the output of any probe call. The same
+ * input gives the same bytes. Asynchronous on stream (NULL = the engine's), three launches, no
+ * allocation: d_scratch (8-byte aligned) holds rf_amd_found_compact_scratch_bytes(m) bytes
+ * (callable without a device; non-decreasing in m). m == 0 is OK and sets *d_count = 0.
+ * EINVAL: NULL d_count, m >= 2^56, a NULL d_found / d_scratch with m > 0. */
+uint64_t rf_amd_found_compact_scratch_bytes(uint64_t m);
+int rf_amd_found_compact(rf_amd_engine *e, const uint64_t *d_found, uint64_t m,
+                         uint64_t *d_cand, uint64_t cap, uint64_t *d_count,
+                         void *d_scratch, void *stream);
 /* The engine's lookup server: single lookups -- routing_filter_lookup (src/routing_filter.h:
  * 87-92) and routing_filter_lookup_async states (:130-155) -- without a kernel launch per
  * call. A persistent wave (started on demand on a queue of its own, exiting after 400 us

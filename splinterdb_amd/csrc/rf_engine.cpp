@@ -2041,6 +2041,123 @@ extern "C" int rf_amd_probe_many_hashes_host(rf_amd_engine* e, rf_amd_batch* con
   return rf_amd_probe_filters_host(e, batches, filter_index, num_groups, h_hashes, gid.data(), n, h_found);
 }
 
+// ---- multi-get: a resident filter set, fan-out probes, candidate lists --------------------
+// The set is the ProbeGroup table of rf_amd_probe_filters_host kept in device memory: member
+// g's probe lines, pages and slots by address. Those buffers stay where they are for the
+// batch's lifetime -- rf_amd_batch_trim keeps d_lines, d_pages and d_slots and releases only the
+// others -- so a set outlives a trim of its members without re-resolving anything.
+extern "C" int rf_launch_probe_fanout(void* stream, int kind, const void* in0, uint32_t key_len, uint32_t seed,
+                                      const ProbeGroup* groups, uint32_t ng, const uint32_t* member, uint32_t K,
+                                      uint64_t n, uint64_t* found);
+extern "C" uint64_t rf_found_compact_tiles(uint64_t m);
+extern "C" int rf_launch_found_compact(void* stream, const uint64_t* found, uint64_t m, uint64_t* cand, uint64_t cap,
+                                       uint64_t* count, void* scratch);
+
+struct rf_amd_filter_set {
+  rf_amd_engine* eng = nullptr;
+  uint32_t num_members = 0;
+  uint32_t seed = 0;       // of every non-NULL member, when they agree
+  bool one_seed = true;
+  DevBuf d_groups;
+};
+
+extern "C" int rf_amd_filter_set_create(rf_amd_engine* e, rf_amd_batch* const* batches, const uint32_t* filter_index,
+                                        uint32_t num_members, rf_amd_filter_set** out) {
+  if (!e) return fail(RF_AMD_ENODEV, "no engine");
+  if (!out) return fail(RF_AMD_EINVAL, "null out-param");
+  *out = nullptr;
+  if (num_members && !batches) return fail(RF_AMD_EINVAL, "null member arrays");
+  HIPCHK(hipSetDevice(e->device));
+  auto s = std::make_unique<rf_amd_filter_set>();
+  s->eng = e;
+  s->num_members = num_members;
+  std::vector<ProbeGroup> groups(num_members);
+  bool any = false;
+  for (uint32_t g = 0; g < num_members; g++) {
+    rf_amd_batch* b = batches[g];
+    if (!b) {  // NULL_ROUTING_FILTER: finds nothing
+      memset(&groups[g], 0, sizeof(ProbeGroup));
+      groups[g].err = 1;
+      continue;
+    }
+    const uint32_t f = filter_index ? filter_index[g] : 0u;
+    if (!b->built || b->eng != e) return fail(RF_AMD_EINVAL, "member on an unbuilt or foreign batch");
+    if (f >= b->F) return fail(RF_AMD_EINVAL, "bad filter index");
+    if (int rc = batch_errors(b)) return rc;
+    groups[g] = probe_group_of(b, f);
+    if (!any) s->seed = b->cfg.seed;
+    else if (b->cfg.seed != s->seed) s->one_seed = false;
+    any = true;
+  }
+  if (s->d_groups.alloc(sizeof(ProbeGroup) * num_members, &e->pool)) return RF_AMD_ENOMEM;
+  if (num_members) {
+    HIPCHK(hipMemcpyAsync(s->d_groups.p, groups.data(), sizeof(ProbeGroup) * num_members, hipMemcpyHostToDevice,
+                          e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));  // `groups` is pageable; probes may run on any stream
+  }
+  *out = s.release();
+  return 0;
+}
+
+// synchronises the device (probes on a caller's stream may still read the table), as
+// rf_amd_batch_destroy does
+extern "C" void rf_amd_filter_set_destroy(rf_amd_filter_set* s) {
+  if (!s) return;
+  (void)hipSetDevice(s->eng->device);
+  (void)hipDeviceSynchronize();
+  delete s;
+}
+
+extern "C" uint32_t rf_amd_filter_set_num_members(const rf_amd_filter_set* s) { return s ? s->num_members : 0; }
+
+static int set_probe(rf_amd_filter_set* s, int kind, const void* in0, uint32_t key_len, const uint32_t* d_member,
+                     uint32_t K, uint64_t n, uint64_t* d_found, void* stream) {
+  if (!s) return fail(RF_AMD_EINVAL, "null filter set");
+  if (K == 0) return fail(RF_AMD_EINVAL, "K == 0");
+  if (!d_member && K != s->num_members) return fail(RF_AMD_EINVAL, "all-members form: K must equal num_members");
+  if (kind != IN_HASH && !s->one_seed) return fail(RF_AMD_EINVAL, "keys form over members with different seeds");
+  if (n > ((1ull << 56) - 1) / K) return fail(RF_AMD_EINVAL, "n * K >= 2^56");
+  if (n == 0) return 0;
+  if (!in0 || !d_found) return fail(RF_AMD_EINVAL, "null probe buffer");
+  HIPCHK(hipSetDevice(s->eng->device));
+  (void)hipGetLastError();
+  int rc = rf_launch_probe_fanout(stream ? stream : s->eng->stream, kind, in0, key_len, s->seed,
+                                  s->d_groups.as<ProbeGroup>(), s->num_members, d_member, K, n, d_found);
+  if (rc) return fail(RF_AMD_EINVAL, std::string("fan-out probe launch: ") + hipGetErrorString((hipError_t)rc));
+  return 0;
+}
+
+extern "C" int rf_amd_filter_set_probe_keys(rf_amd_filter_set* s, const void* d_keys, uint32_t key_len,
+                                            const uint32_t* d_member, uint32_t K, uint64_t n, uint64_t* d_found,
+                                            void* stream) {
+  if (key_len == 0) return fail(RF_AMD_EINVAL, "key_len 0");
+  return set_probe(s, fixed_kind(d_keys, key_len), d_keys, key_len, d_member, K, n, d_found, stream);
+}
+extern "C" int rf_amd_filter_set_probe_hashes(rf_amd_filter_set* s, const uint32_t* d_hashes, const uint32_t* d_member,
+                                              uint32_t K, uint64_t n, uint64_t* d_found, void* stream) {
+  return set_probe(s, IN_HASH, d_hashes, 4, d_member, K, n, d_found, stream);
+}
+
+// 8 bytes of offset and 4 of count per tile of found words, and slack to keep both aligned
+extern "C" uint64_t rf_amd_found_compact_scratch_bytes(uint64_t m) {
+  return ((12 * rf_found_compact_tiles(m) + 15) & ~15ull) + 16;
+}
+
+extern "C" int rf_amd_found_compact(rf_amd_engine* e, const uint64_t* d_found, uint64_t m, uint64_t* d_cand,
+                                    uint64_t cap, uint64_t* d_count, void* d_scratch, void* stream) {
+  if (!e) return fail(RF_AMD_ENODEV, "no engine");
+  if (!d_count) return fail(RF_AMD_EINVAL, "null count");
+  if (m >= (1ull << 56)) return fail(RF_AMD_EINVAL, "m >= 2^56");
+  if (m && (!d_found || !d_scratch)) return fail(RF_AMD_EINVAL, "null found words / scratch");
+  if (m && cap && !d_cand) return fail(RF_AMD_EINVAL, "null candidate buffer");
+  if ((uintptr_t)d_scratch & 7) return fail(RF_AMD_EINVAL, "scratch not 8-byte aligned");
+  HIPCHK(hipSetDevice(e->device));
+  (void)hipGetLastError();
+  int rc = rf_launch_found_compact(stream ? stream : e->stream, d_found, m, d_cand, cap, d_count, d_scratch);
+  if (rc) return fail(RF_AMD_EINVAL, std::string("compaction launch: ") + hipGetErrorString((hipError_t)rc));
+  return 0;
+}
+
 static int do_probe(rf_amd_batch* b, int kind, const void* in0, const uint64_t* offs, uint32_t key_len,
                     const uint32_t* fid, uint64_t n, uint64_t* found, void* stream,
                     const uint64_t* d_runs) {

@@ -24,6 +24,8 @@
 // Probe lines: k_plines, one wave per index: device-only 64-byte lines per bucket group
 //                     cut from the image (see "probe lines" below)
 // Probe: k_probe, one lane per probe (routing_filter_lookup, :986-1073).
+// Multi-get: k_probe_fanout, every key against K filters of a resident set of any batches;
+//                     k_found_count / _scan / _emit, found words -> ordered candidate list.
 //
 // The coarse bucket of an entry is its top `cbits` bits; K4 sorts the low bits, so the
 // result depends only on the multiset of entries, exactly like the reference's sort.
@@ -4297,6 +4299,271 @@ __global__ __launch_bounds__(WAVE) void k_probe_small(SmallProbe a) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __hip_atomic_store(a.done_flag, a.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
   }
+}
+
+// ---- multi-get: fan-out probes over a resident filter set ------------------------------
+// Key i is looked up in K members of a ProbeGroup table (rf_amd_filter_set_probe_*): the maplets
+// along its trunk path (trunk_merge_lookup, src/trunk.c:6008-6075), filters of any batches. A
+// wave takes 64 consecutive keys and hashes them one per lane -- each key is read and hashed
+// once, 24-byte keys staged through LDS as k_probe stages them -- and parks the hashes in LDS.
+// It then walks its 64 K (key, slot) pairs in row-major order, 64 per step: lane p of a step
+// handles key p / K, slot p % K, so member ids are read and found words stored coalesced
+// (non-temporal, as k_probe's). FAN_U steps go together: their member ids, then their group
+// heads, then their probe lines are requested before the first line is decoded. A pair whose
+// line cannot answer (overflowed, none) takes probe_group, line and image walk, as
+// k_probe_groups does. member == nullptr: slot j is member j (K == ng), no id array is read.
+// The last, partial wave and the pairs past n K are masked.
+constexpr int FAN_NT = 256;
+#ifndef RF_FAN_U
+#define RF_FAN_U 2
+#endif
+constexpr int FAN_U = RF_FAN_U;  // steps whose loads are in flight together
+
+template <int KIND>
+__global__ __launch_bounds__(FAN_NT) void k_probe_fanout(const void* __restrict__ in0, uint32_t key_len,
+                                                         uint32_t seed, const ProbeGroup* __restrict__ groups,
+                                                         uint32_t ng, const uint32_t* __restrict__ member,
+                                                         uint32_t K, uint64_t n, uint64_t* __restrict__ found) {
+  constexpr bool WAVE_KEYS = KIND == IN_KEYS24;
+  constexpr int NW = FAN_NT / WAVE;
+  __shared__ v4u s_keys[NW][WAVE_KEYS ? 96 : 1];
+  __shared__ uint32_t s_h[NW][WAVE];
+  const uint32_t lane = threadIdx.x & (WAVE - 1);
+  const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x) / WAVE;
+  const uint64_t nwaves = (n + WAVE - 1) / WAVE;
+  const uint32_t q64 = WAVE / K, r64 = WAVE % K;  // a step of 64 pairs = q64 keys and r64 slots
+  for (uint64_t wc = (uint64_t)blockIdx.x * NW + wv; wc < nwaves; wc += (uint64_t)gridDim.x * NW) {
+    const uint64_t wf = wc * WAVE;  // the wave's first key (wave-uniform)
+    const uint32_t nk = (uint32_t)min<uint64_t>(WAVE, n - wf);
+    uint32_t h = 0;
+    if constexpr (WAVE_KEYS) {
+      if (((uintptr_t)in0 & 15) == 0) {
+        v4u* sw = s_keys[wv];
+        const v4u* src = reinterpret_cast<const v4u*>(static_cast<const uint8_t*>(in0) + wf * 24);
+        if (nk == WAVE) {  // 1,536 contiguous bytes by LDS-DMA (probe_fast)
+          __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + lane),
+                                           (__attribute__((address_space(3))) void*)sw, 16, 0, 2);
+          if (lane < 32)
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + WAVE + lane),
+                                             (__attribute__((address_space(3))) void*)(sw + WAVE), 16, 0, 2);
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        } else {
+          const uint32_t bytes = nk * 24;
+#pragma unroll
+          for (uint32_t j = lane; j < 96; j += WAVE) {
+            if ((j + 1) * 16 <= bytes) {
+              sw[j] = __builtin_nontemporal_load(src + j);
+            } else if (j * 16 < bytes) {  // an odd key count ends on an 8-byte half
+              const uint64_t t = __builtin_nontemporal_load(reinterpret_cast<const uint64_t*>(src + j));
+              sw[j] = v4u{(uint32_t)t, (uint32_t)(t >> 32), 0u, 0u};
+            }
+          }
+        }
+        wave_sync_lds();
+        if (lane < nk) {
+          const uint2* k2 = reinterpret_cast<const uint2*>(sw) + 3 * lane;
+          const uint2 a = k2[0], b = k2[1], c = k2[2];
+          const uint32_t w[6] = {a.x, a.y, b.x, b.y, c.x, c.y};
+          h = xxh32_24(w, seed);
+        }
+      } else if (lane < nk) {
+        h = hash_key<KIND, true>(in0, nullptr, key_len, seed, wf + lane);
+      }
+    } else {
+      if (lane < nk) h = hash_key<KIND, true>(in0, nullptr, key_len, seed, wf + lane);
+    }
+    s_h[wv][lane] = h;
+    wave_sync_lds();
+    const uint64_t pbase = wf * K;          // the wave's first pair (n K < 2^56)
+    const uint64_t np = (uint64_t)nk * K;   // its pairs
+    uint32_t key = lane / K, slot = lane % K;
+    for (uint64_t p0 = lane; p0 < np + lane; p0 += (uint64_t)WAVE * FAN_U) {  // p0 - lane: wave-uniform
+      uint32_t kk[FAN_U], g[FAN_U], st[FAN_U], px[FAN_U], pf[FAN_U], hh[FAN_U], pj[FAN_U], pr[FAN_U];
+      v4u Q[FAN_U][4];
+      // member ids: one coalesced row-major read per step (or the slot itself)
+#pragma unroll
+      for (int u = 0; u < FAN_U; u++) {
+        kk[u] = key;
+        g[u] = 0xffffffffu;
+        if (key < nk) g[u] = member ? __builtin_nontemporal_load(member + pbase + p0 + (uint64_t)u * WAVE) : slot;
+        const uint64_t s2 = (uint64_t)slot + r64;
+        key += q64 + (s2 >= K ? 1u : 0u);
+        slot = (uint32_t)(s2 >= K ? s2 - K : s2);
+      }
+      // group heads: scalar loads through the constant address space when the whole wave names
+      // one member, one plain load per lane otherwise
+      uint64_t pl[FAN_U];
+#pragma unroll
+      for (int u = 0; u < FAN_U; u++) {
+        if (g[u] >= ng) g[u] = 0xffffffffu;  // NULL_ROUTING_FILTER by position: finds nothing
+        const uint32_t gs = __builtin_amdgcn_readfirstlane(g[u]);
+        uint32_t err = 1;
+        px[u] = pf[u] = 0;
+        pl[u] = 0;
+        if (__builtin_amdgcn_ballot_w64(g[u] != gs) == 0) {
+          if (gs != 0xffffffffu) {
+            const ProbeGroup* G = groups + gs;
+            px[u] = sload32(&G->x);
+            err = sload32(&G->err);
+            pf[u] = sload32(&G->fpl);
+            pl[u] = sload64(&G->lines);
+          }
+        } else if (g[u] != 0xffffffffu) {
+          const ProbeGroup* G = groups + g[u];
+          px[u] = G->x;
+          err = G->err;
+          pf[u] = G->fpl;
+          pl[u] = (uint64_t)(uintptr_t)G->lines;
+        }
+        st[u] = err ? 0u : ((px[u] >> 24) ? 1u : 2u);  // 0 nothing found, 1 probe line, 2 no lines: walk
+      }
+      // probe lines (probe_line's addressing)
+#pragma unroll
+      for (int u = 0; u < FAN_U; u++) {
+        hh[u] = s_h[wv][kk[u] & (WAVE - 1)];
+        pj[u] = pr[u] = 0;
+        if (st[u] == 1) {
+          const uint32_t rem = (px[u] >> 8) & 0xff, lgl = px[u] >> 24, fp_size = pf[u] & 0xff;
+          const uint32_t fp = hh[u] >> (32 - fp_size);
+          const uint32_t bucket = rem >= 32 ? 0u : fp >> rem;
+          pr[u] = fp & (rem >= 32 ? 0xffffffffu : ((1u << rem) - 1));
+          pj[u] = bucket & ((1u << (lgl - 1)) - 1);
+          const v4u* lp = reinterpret_cast<const v4u*>((uintptr_t)pl[u]) + (uint64_t)(bucket >> (lgl - 1)) * 4;
+#pragma unroll
+          for (int k = 0; k < 4; k++) Q[u][k] = lp[k];
+        }
+      }
+      // decode and store
+#pragma unroll
+      for (int u = 0; u < FAN_U; u++) {
+        uint64_t r = 0;
+        bool walk = st[u] == 2;
+        if (st[u] == 1) walk = !line_decode(Q[u], pj[u], pr[u], px[u] & 0xff, (px[u] >> 16) & 0xff, r);
+        if (walk) r = probe_group(groups[g[u]], hh[u]);
+        if (kk[u] < nk) __builtin_nontemporal_store(r, found + pbase + p0 + (uint64_t)u * WAVE);
+      }
+    }
+    wave_sync_lds();  // the next chunk's keys and hashes overwrite this one's
+  }
+}
+
+// ---- multi-get: found_values words -> ordered candidate list ---------------------------
+// The set bits of m found words as records index << 8 | value, index ascending and, within a
+// word, value descending (routing_filter_get_next_value's order, src/routing_filter.h:94-105):
+// the (key, bundle, branch) candidates of the loop around it (src/trunk.c:6057-6060). Three
+// stream-ordered launches, like the route kernels, without communication between workgroups:
+// k_found_count (popcount sum per tile), k_found_scan (exclusive scan of the tile sums by one
+// workgroup, the total to *count), k_found_emit (re-reads its tile, scans the popcounts in the
+// workgroup, writes each word's records at its scanned position, below cap only).
+constexpr int FC_NT = 256;
+constexpr int FC_PER = 16;
+constexpr uint32_t FC_TILE = FC_NT * FC_PER;  // found words per tile: a tile sum fits 2^18
+constexpr uint32_t FC_MAX_GRID = 1u << 20;
+
+__global__ __launch_bounds__(FC_NT) void k_found_count(const uint64_t* __restrict__ found, uint64_t m,
+                                                       uint64_t ntiles, uint32_t* __restrict__ cnt) {
+  __shared__ uint32_t s_c[FC_NT / WAVE];
+  for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const uint64_t t0 = t * FC_TILE;
+    uint32_t c = 0;
+#pragma unroll
+    for (int k = 0; k < FC_PER; k++) {
+      const uint64_t i = t0 + (uint64_t)k * FC_NT + threadIdx.x;
+      if (i < m) c += (uint32_t)__popcll(found[i]);
+    }
+    c = wave_incl_scan(c);
+    if ((threadIdx.x & (WAVE - 1)) == WAVE - 1) s_c[threadIdx.x / WAVE] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      uint32_t s = 0;
+      for (int w = 0; w < FC_NT / WAVE; w++) s += s_c[w];
+      cnt[t] = s;
+    }
+    __syncthreads();
+  }
+}
+
+// exclusive scan of the tile sums (chunks of 1,024: a chunk's total fits 32 bits) into 64-bit
+// offsets; *count = the total (ntiles == 0: 0)
+__global__ __launch_bounds__(1024) void k_found_scan(const uint32_t* __restrict__ cnt, uint64_t ntiles,
+                                                     uint64_t* __restrict__ off, uint64_t* __restrict__ count) {
+  __shared__ uint32_t s_tmp[1024 / WAVE + 1];
+  uint64_t carry = 0;
+  for (uint64_t base = 0; base < ntiles; base += 1024) {
+    const uint64_t i = base + threadIdx.x;
+    const uint32_t x = i < ntiles ? cnt[i] : 0u;
+    uint32_t tot;
+    const uint32_t r = block_excl_scan<1024>(x, s_tmp, &tot);
+    if (i < ntiles) off[i] = carry + r;
+    carry += tot;
+  }
+  if (threadIdx.x == 0) *count = carry;
+}
+
+__global__ __launch_bounds__(FC_NT) void k_found_emit(const uint64_t* __restrict__ found, uint64_t m,
+                                                      uint64_t ntiles, const uint64_t* __restrict__ off,
+                                                      uint64_t* __restrict__ cand, uint64_t cap) {
+  __shared__ uint32_t s_w[FC_PER * (FC_NT / WAVE) + 1];
+  for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const uint64_t t0 = t * FC_TILE;
+    uint64_t w[FC_PER];
+    uint32_t x[FC_PER];
+#pragma unroll
+    for (int k = 0; k < FC_PER; k++) {
+      const uint64_t i = t0 + (uint64_t)k * FC_NT + threadIdx.x;
+      w[k] = i < m ? found[i] : 0ull;
+      x[k] = (uint32_t)__popcll(w[k]);
+    }
+    uint32_t tot;
+    block_excl_scan_kmajor<FC_NT, FC_PER>(x, s_w, &tot);  // word order: k-major, thread-minor
+    const uint64_t base = off[t];
+    if (tot == 0 || base >= cap) continue;  // uniform over the workgroup
+#pragma unroll
+    for (int k = 0; k < FC_PER; k++) {
+      const uint64_t rec = (t0 + (uint64_t)k * FC_NT + threadIdx.x) << 8;
+      uint64_t pos = base + x[k], v = w[k];
+      while (v && pos < cap) {  // from the highest value down
+        const uint32_t b = 63u - (uint32_t)__builtin_clzll(v);
+        cand[pos++] = rec | b;
+        v &= ~(1ull << b);
+      }
+    }
+  }
+}
+
+extern "C" uint64_t rf_found_compact_tiles(uint64_t m) { return (m + FC_TILE - 1) / FC_TILE; }
+
+// scratch: ntiles 64-bit offsets, then ntiles 32-bit sums
+extern "C" int rf_launch_found_compact(void* stream, const uint64_t* found, uint64_t m, uint64_t* cand, uint64_t cap,
+                                       uint64_t* count, void* scratch) {
+  const uint64_t ntiles = rf_found_compact_tiles(m);
+  uint64_t* off = static_cast<uint64_t*>(scratch);
+  uint32_t* cnt = reinterpret_cast<uint32_t*>(off + ntiles);
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 g((uint32_t)(ntiles < FC_MAX_GRID ? ntiles : FC_MAX_GRID));
+  if (ntiles) hipLaunchKernelGGL(k_found_count, g, dim3(FC_NT), 0, st, found, m, ntiles, cnt);
+  hipLaunchKernelGGL(k_found_scan, dim3(1), dim3(1024), 0, st, cnt, ntiles, off, count);
+  if (ntiles && cap) hipLaunchKernelGGL(k_found_emit, g, dim3(FC_NT), 0, st, found, m, ntiles, off, cand, cap);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : (int)e;
+}
+
+extern "C" int rf_launch_probe_fanout(void* stream, int kind, const void* in0, uint32_t key_len, uint32_t seed,
+                                      const ProbeGroup* groups, uint32_t ng, const uint32_t* member, uint32_t K,
+                                      uint64_t n, uint64_t* found) {
+  if (n == 0) return 0;
+  const uint64_t nblk = ((n + WAVE - 1) / WAVE + FAN_NT / WAVE - 1) / (FAN_NT / WAVE);
+  const dim3 g((uint32_t)(nblk < 0x7fffffffull ? nblk : 0x7fffffffull)), b(FAN_NT);
+#define L(KD) hipLaunchKernelGGL((k_probe_fanout<KD>), g, b, 0, (hipStream_t)stream, in0, key_len, seed, groups, ng, member, K, n, found)
+  switch (kind) {
+    case IN_KEYS24: L(IN_KEYS24); break;
+    case IN_KEYS_W: L(IN_KEYS_W); break;
+    case IN_KEYS_B: L(IN_KEYS_B); break;
+    default: L(IN_HASH); break;
+  }
+#undef L
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : (int)e;
 }
 
 // ---- the lookup server ---------------------------------------------------------------------

@@ -57,8 +57,12 @@ EXPORTED = [
     "rf_amd_batch_stage_abort", "rf_amd_lookup_server_error", "rf_amd_lookup_server_failed",
     "rf_amd_lookup_server_set_times", "rf_amd_diag_lookup_server_kill", "rf_amd_diag_lookup_ring",
     "rf_amd_batch_create_runs", "rf_amd_filter_add_runs", "rf_amd_diag_k4_bitmap_builds",
+    "rf_amd_filter_set_create", "rf_amd_filter_set_destroy", "rf_amd_filter_set_num_members",
+    "rf_amd_filter_set_probe_keys", "rf_amd_filter_set_probe_hashes",
+    "rf_amd_found_compact_scratch_bytes", "rf_amd_found_compact",
 ]
 ROUTE_MAX_WORLD = 16
+FOUND_COMPACT_TILE = 4096  # found words per workgroup of rf_amd_found_compact (FC_TILE)
 ASYNC_STATUS_RUNNING = 0  # src/platform_linux/async.h:137-140
 ASYNC_STATUS_DONE = 1
 CALLBACK_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p)
@@ -223,6 +227,16 @@ def load_library(build_if_missing=True):
     L.rf_amd_batch_stage_build.argtypes = [vp]
     L.rf_amd_batch_stage_abort.argtypes = [vp]
     L.rf_amd_batch_stage_abort.restype = None
+    L.rf_amd_filter_set_create.argtypes = [vp, vp, vp, u32, ctypes.POINTER(vp)]
+    L.rf_amd_filter_set_destroy.argtypes = [vp]
+    L.rf_amd_filter_set_destroy.restype = None
+    L.rf_amd_filter_set_num_members.argtypes = [vp]
+    L.rf_amd_filter_set_num_members.restype = u32
+    L.rf_amd_filter_set_probe_keys.argtypes = [vp, vp, u32, vp, u32, u64, vp, vp]
+    L.rf_amd_filter_set_probe_hashes.argtypes = [vp, vp, vp, u32, u64, vp, vp]
+    L.rf_amd_found_compact_scratch_bytes.argtypes = [u64]
+    L.rf_amd_found_compact_scratch_bytes.restype = u64
+    L.rf_amd_found_compact.argtypes = [vp, vp, u64, vp, u64, vp, vp, vp]
     _lib = L
     return L
 
@@ -847,3 +861,107 @@ class FilterBatch:
                                                       slots.ctypes.data, slots.size))
         return RoutingFilter(inf.num_fingerprints, inf.num_unique, inf.value_size,
                              inf.num_indices, inf.num_pages, pages, slots)
+
+
+# ---- multi-get: filter sets, fan-out probes, candidate lists -----------------------------
+def found_candidates(found: np.ndarray) -> np.ndarray:
+    """Host mirror of rf_amd_found_compact: the set bits of the found_values words as records
+    index << 8 | value (uint64), index ascending and, within a word, value descending -- the
+    order in which routing_filter_get_next_value hands a word's values out."""
+    w = np.ascontiguousarray(found).reshape(-1).view(np.uint64)
+    nz = np.flatnonzero(w)
+    if nz.size == 0:
+        return np.zeros(0, dtype=np.uint64)
+    # byte-wise big-endian view: unpackbits then lists bit 63 first
+    bits = np.unpackbits(w[nz].astype(">u8").view(np.uint8).reshape(-1, 8), axis=1)
+    row, col = np.nonzero(bits)  # row-major: value = 63 - col descends within a word
+    return (nz[row].astype(np.uint64) << np.uint64(8)) | (np.uint64(63) - col.astype(np.uint64))
+
+
+def found_compact_scratch_bytes(m) -> int:
+    return int(load_library().rf_amd_found_compact_scratch_bytes(m))
+
+
+_compact_scratch = {}  # (engine, stream) -> the scratch of the last found_compact issued there
+
+
+def found_compact(d_found, m, d_cand, d_count, stream=None, engine=None):
+    """rf_amd_found_compact: the candidate records of d_found[:m] into d_cand (capacity: its
+    length; None: count only) and their total number into d_count (a device uint64 / int64 of
+    one element), asynchronously. The scratch is a torch buffer kept until the next call on the
+    same stream."""
+    import torch
+    eng = engine or default_engine()
+    st = _stream(stream)
+    ref = d_found if hasattr(d_found, "device") else d_count
+    scratch = torch.empty(found_compact_scratch_bytes(m) // 8, dtype=torch.int64, device=ref.device)
+    cap = 0 if d_cand is None else d_cand.numel()
+    _check(load_library().rf_amd_found_compact(eng.h, _dptr(d_found), m, _dptr(d_cand), cap, _dptr(d_count),
+                                               scratch.data_ptr(), st))
+    _compact_scratch[(id(eng), st)] = scratch
+
+
+class FilterSet:
+    """A resident table of filters of any batches (rf_amd_filter_set): members = [(FilterBatch,
+    index) or None]. The member batches must outlive the set's last probe."""
+
+    def __init__(self, members, engine=None):
+        self.engine = engine or default_engine()
+        n = len(members)
+        hs = (ctypes.c_void_p * max(1, n))()
+        idx = np.zeros(max(1, n), dtype=np.uint32)
+        for i, m in enumerate(members):
+            if m is not None:
+                hs[i] = m[0].h.value
+                idx[i] = m[1]
+        self._keep = [m[0] for m in members if m is not None]
+        self.num_members = n
+        h = ctypes.c_void_p()
+        _check(load_library().rf_amd_filter_set_create(self.engine.h, ctypes.addressof(hs), idx.ctypes.data, n,
+                                                       ctypes.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            load_library().rf_amd_filter_set_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def probe_keys(self, d_keys, key_len, d_member, K, n, d_found, stream=None):
+        """key i in members d_member[i*K : i*K+K] (None: every member, K = num_members) into
+        d_found[i*K : i*K+K]; each key is read and hashed once"""
+        _check(load_library().rf_amd_filter_set_probe_keys(self.h, _dptr(d_keys), key_len, _dptr(d_member), K, n,
+                                                           _dptr(d_found), _stream(stream)))
+
+    def probe_hashes(self, d_hashes, d_member, K, n, d_found, stream=None):
+        _check(load_library().rf_amd_filter_set_probe_hashes(self.h, _dptr(d_hashes), _dptr(d_member), K, n,
+                                                             _dptr(d_found), _stream(stream)))
+
+    def multiget(self, d_keys, key_len, d_member, K, n, cap=None, stream=None):
+        """probe_keys + found_compact: returns (d_cand, count), the first `count` records of
+        d_cand being the candidates key * K + slot << 8 | value in order. One synchronisation;
+        a second compaction and synchronisation when the candidates outnumber `cap` (default:
+        one per key)."""
+        import torch
+        dev = d_keys.device
+        d_found = torch.empty(n * K, dtype=torch.int64, device=dev)
+        self.probe_keys(d_keys, key_len, d_member, K, n, d_found, stream)
+        d_count = torch.zeros(1, dtype=torch.int64, device=dev)
+        d_cand = torch.empty(max(1, n) if cap is None else cap, dtype=torch.int64, device=dev)
+        def read_count():
+            if stream is not None:  # a raw handle torch's own copy is not ordered with
+                torch.cuda.ExternalStream(stream).synchronize()
+            return int(d_count.item())
+
+        found_compact(d_found, n * K, d_cand, d_count, stream, self.engine)
+        count = read_count()
+        if count > d_cand.numel():
+            d_cand = torch.empty(count, dtype=torch.int64, device=dev)
+            found_compact(d_found, n * K, d_cand, d_count, stream, self.engine)
+            count = read_count()
+        return d_cand, count
