@@ -9,22 +9,26 @@ constexpr int WAVE = 64;
 
 // ---- XXH32 (published xxHash algorithm; the reference's platform_hash32,
 //      src/platform_linux/platform_hash.h:23) ----------------------------------------
+// The global-memory hash helpers also compile for the host (tests/c/hash_check.cpp runs them
+// on the CPU under sanitizers); xxh32_lds and everything after it is device-only.
+#define RF_HD __host__ __device__ __forceinline__
+
 constexpr uint32_t XP1 = 2654435761U, XP2 = 2246822519U, XP3 = 3266489917U,
                    XP4 = 668265263U, XP5 = 374761393U;
 
-__device__ __forceinline__ uint32_t rotl32(uint32_t x, int r) {
+RF_HD uint32_t rotl32(uint32_t x, int r) {
   return __builtin_rotateleft32(x, r);
 }
-__device__ __forceinline__ uint32_t xround(uint32_t acc, uint32_t in) {
+RF_HD uint32_t xround(uint32_t acc, uint32_t in) {
   return rotl32(acc + in * XP2, 13) * XP1;
 }
-__device__ __forceinline__ uint32_t xavalanche(uint32_t h) {
+RF_HD uint32_t xavalanche(uint32_t h) {
   h ^= h >> 15; h *= XP2; h ^= h >> 13; h *= XP3; h ^= h >> 16;
   return h;
 }
 
 // 24-byte key held as 6 little-endian words (the filter_test / BASELINE key format)
-__device__ __forceinline__ uint32_t xxh32_24(const uint32_t w[6], uint32_t seed) {
+RF_HD uint32_t xxh32_24(const uint32_t w[6], uint32_t seed) {
   uint32_t v1 = seed + XP1 + XP2, v2 = seed + XP2, v3 = seed, v4 = seed - XP1;
   v1 = xround(v1, w[0]); v2 = xround(v2, w[1]); v3 = xround(v3, w[2]); v4 = xround(v4, w[3]);
   uint32_t h = rotl32(v1, 1) + rotl32(v2, 7) + rotl32(v3, 12) + rotl32(v4, 18);
@@ -35,7 +39,7 @@ __device__ __forceinline__ uint32_t xxh32_24(const uint32_t w[6], uint32_t seed)
 }
 
 // Generic length, 4-byte aligned base: word loads.
-__device__ __forceinline__ uint32_t xxh32_words(const uint32_t* p, uint32_t len, uint32_t seed) {
+RF_HD uint32_t xxh32_words(const uint32_t* p, uint32_t len, uint32_t seed) {
   uint32_t h, i = 0;
   if (len >= 16) {
     uint32_t v1 = seed + XP1 + XP2, v2 = seed + XP2, v3 = seed, v4 = seed - XP1;
@@ -64,17 +68,17 @@ __device__ __forceinline__ uint32_t xxh32_words(const uint32_t* p, uint32_t len,
 // Arbitrary alignment: gfx950 global loads accept unaligned addresses, so each 16-byte
 // stripe is ONE dwordx4 load (memcpy lets the compiler emit it) and every load stays inside
 // the key's own bytes.
-__device__ __forceinline__ uint32_t pick4u(uint32_t q, uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
+RF_HD uint32_t pick4u(uint32_t q, uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
   return q == 0 ? a : q == 1 ? b : q == 2 ? c : d;
 }
 
-__device__ __forceinline__ uint32_t xxh32_unaligned(const uint8_t* p, uint32_t len, uint32_t seed);
+RF_HD uint32_t xxh32_unaligned(const uint8_t* p, uint32_t len, uint32_t seed);
 
 // One key per lane with nothing else in flight (probes, k_hash): for keys of 16..128 bytes
 // every load of the key is issued before any is used; other lengths take xxh32_unaligned.
 // (The partition keeps the stripe loop: it hashes 8 keys per lane at once, and the extra
 // registers cost it more than the loop's waits.)
-__device__ __forceinline__ uint32_t xxh32_unaligned_prefetch(const uint8_t* p, uint32_t len, uint32_t seed) {
+RF_HD uint32_t xxh32_unaligned_prefetch(const uint8_t* p, uint32_t len, uint32_t seed) {
   constexpr uint32_t MS = 8;
   if (len >= 16 && len <= 16 * MS) {
     // Every load of the key is issued before any is used (a stripe loop would wait for
@@ -120,7 +124,7 @@ __device__ __forceinline__ uint32_t xxh32_unaligned_prefetch(const uint8_t* p, u
   return xxh32_unaligned(p, len, seed);
 }
 
-__device__ __forceinline__ uint32_t xxh32_unaligned(const uint8_t* p, uint32_t len, uint32_t seed) {
+RF_HD uint32_t xxh32_unaligned(const uint8_t* p, uint32_t len, uint32_t seed) {
   uint32_t h, i = 0;
   if (len >= 16) {
     uint32_t v1 = seed + XP1 + XP2, v2 = seed + XP2, v3 = seed, v4 = seed - XP1;

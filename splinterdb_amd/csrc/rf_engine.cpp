@@ -1082,13 +1082,6 @@ static int do_build(rf_amd_batch* b, int kind, const void* in0, const uint64_t* 
   return 0;
 }
 
-static int fixed_kind(const void* p, uint32_t key_len) {
-  const uintptr_t u = (uintptr_t)p;
-  if (key_len == 24 && (u & 7) == 0) return IN_KEYS24;
-  if ((key_len & 3) == 0 && (u & 3) == 0) return IN_KEYS_W;
-  return IN_KEYS_B;
-}
-
 extern "C" int rf_amd_batch_build_keys(rf_amd_batch* b, const void* d_keys, uint32_t key_len, void* stream) {
   if (key_len == 0) return fail(RF_AMD_EINVAL, "key_len 0");
   return do_build(b, fixed_kind(d_keys, key_len), d_keys, nullptr, key_len, stream);

@@ -496,7 +496,7 @@ __global__ __launch_bounds__(SCAT_NT) __attribute__((amdgpu_waves_per_eu(RF_SCAT
       for (int k = 0; k < HASH_CHUNK; k++) {
         const uint32_t j = min(threadIdx.x + (k0 + k) * SCAT_NT, count - 1) + dep;
         const v2u* kp = reinterpret_cast<const v2u*>(static_cast<const uint8_t*>(in0) +
-                                                     (P.key_first + start + j) * 24);
+                                                     (uint64_t)(P.key_first + start + j) * 24);
         ka[k] = kp[0];
         kb[k] = kp[1];
         kc[k] = kp[2];

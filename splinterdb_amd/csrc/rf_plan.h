@@ -41,6 +41,16 @@ constexpr uint32_t ASM_GT = 1024;   // group-start table entries per page (lines
 
 enum InputKind { IN_KEYS24 = 0, IN_KEYS_W = 1, IN_KEYS_B = 2, IN_VAR = 3, IN_HASH = 4, IN_PAIR = 5 };
 
+// The reader of fixed-length keys at `p` (hash_key in rf_kernels.hip): 24-byte keys as three
+// 8-byte loads, whole words from a 4-byte aligned base, else loads of any alignment. Key k lies
+// at p + k * key_len, so the length must keep every key as aligned as the base.
+inline int fixed_kind(const void* p, uint32_t key_len) {
+  const uintptr_t u = (uintptr_t)p;
+  if (key_len == 24 && (u & 7) == 0) return IN_KEYS24;
+  if ((key_len & 3) == 0 && (u & 3) == 0) return IN_KEYS_W;
+  return IN_KEYS_B;
+}
+
 constexpr uint32_t ERR_INDEX_OVERFLOW = 1u, ERR_BLOCK_TOO_BIG = 2u, ERR_PAGE_CAP = 4u,
                    ERR_GEOMETRY = 8u;
 
