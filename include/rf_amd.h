@@ -127,6 +127,11 @@ int rf_amd_batch_probe_keys_runs(rf_amd_batch *b, const void *d_keys, uint32_t k
                                  const uint64_t *h_counts, uint64_t *d_found, void *stream);
 int rf_amd_batch_probe_hashes_runs(rf_amd_batch *b, const uint32_t *d_hashes, const uint64_t *h_counts,
                                    uint64_t *d_found, void *stream);
+/* the same for variable-length keys: the sum of h_counts keys, key i being
+ * d_bytes[d_offsets[i] .. d_offsets[i+1]) as in rf_amd_batch_probe_var_keys */
+int rf_amd_batch_probe_var_keys_runs(rf_amd_batch *b, const uint8_t *d_bytes,
+                                     const uint64_t *d_offsets, const uint64_t *h_counts,
+                                     uint64_t *d_found, void *stream);
 
 /* Host-buffer forms (synchronous), for callers that hold no device memory, e.g. the
  * routing_filter.h shim (shim/routing_filter_amd.c): build batch b from its keys_total host
@@ -201,6 +206,15 @@ int rf_amd_filter_set_probe_keys(rf_amd_filter_set *s, const void *d_keys, uint3
 int rf_amd_filter_set_probe_hashes(rf_amd_filter_set *s, const uint32_t *d_hashes,
                                    const uint32_t *d_member, uint32_t K, uint64_t n,
                                    uint64_t *d_found, void *stream);
+/* the keys form for variable-length keys (SplinterDB's key slices): key i is
+ * d_bytes[d_offsets[i] .. d_offsets[i+1]), d_offsets holding n + 1 non-decreasing byte offsets
+ * (unchecked, as in rf_amd_batch_probe_var_keys). d_bytes may have any alignment, d_offsets[0]
+ * need not be 0, a zero-length key is legal (XXH32 of nothing). Everything else -- members,
+ * d_found, the seed rule, the EINVAL cases (a NULL d_bytes, d_offsets or d_found with n > 0),
+ * n == 0, asynchronous without allocation or synchronisation -- is rf_amd_filter_set_probe_keys'. */
+int rf_amd_filter_set_probe_var_keys(rf_amd_filter_set *s, const uint8_t *d_bytes,
+                                     const uint64_t *d_offsets, const uint32_t *d_member,
+                                     uint32_t K, uint64_t n, uint64_t *d_found, void *stream);
 /* the set bits of m found_values words as an ordered candidate list: record =
  * index << 8 | value, index ascending, and within one word value DESCENDING (the order in
  * which routing_filter_get_next_value hands them out, src/routing_filter.h:94-105; with the
@@ -390,6 +404,12 @@ int  rf_amd_filter_lookup_hashes(rf_amd_engine *e, const rf_amd_config *cfg,
 int  rf_amd_filter_lookup_keys(rf_amd_engine *e, const rf_amd_config *cfg,
                                const rf_amd_image *filter, const void *keys, uint32_t key_len,
                                uint64_t n, uint64_t *found_values);
+/* the same for variable-length keys in host memory: key i is bytes[offsets[i] .. offsets[i+1]),
+ * offsets holding n + 1 non-decreasing byte offsets. Only the byte range the keys occupy,
+ * offsets[n] - offsets[0] bytes, is copied to the device, so offsets[0] may be large. */
+int  rf_amd_filter_lookup_var_keys(rf_amd_engine *e, const rf_amd_config *cfg,
+                                   const rf_amd_image *filter, const uint8_t *bytes,
+                                   const uint64_t *offsets, uint64_t n, uint64_t *found_values);
 void rf_amd_image_free(rf_amd_image *img);
 
 /* ---- routing_filter_estimate_unique_fp (src/routing_filter.h:169-175, .c:702-848) ------

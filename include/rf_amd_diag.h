@@ -64,6 +64,12 @@ int rf_amd_diag_lookup_server_kill(rf_amd_engine *e, int err, uint32_t gap_us);
  * see which of the two the build took */
 uint64_t rf_amd_diag_k4_bitmap_builds(void);
 
+/* process-wide cap on the grid of the fan-out probe (rf_amd_filter_set_probe_*), in workgroups
+ * of 256 keys; 0 restores the default, a grid that covers n. With a cap below n / 256 every
+ * wave takes several 64-key chunks, so a test of a few thousand keys runs the kernel's
+ * grid-stride loop, which otherwise starts only above 2^31 workgroups. Always returns 0. */
+int rf_amd_diag_fanout_max_blocks(uint32_t blocks);
+
 /* the source id the library was built from (16 hex digits of SHA-256 over the engine's
  * sources and headers, splinterdb_amd/build.py source_id): the Python loader refuses a
  * library whose id differs from the tree's (a stale prebuilt .so) */

@@ -2039,9 +2039,10 @@ extern "C" int rf_amd_probe_many_hashes_host(rf_amd_engine* e, rf_amd_batch* con
 // g's probe lines, pages and slots by address. Those buffers stay where they are for the
 // batch's lifetime -- rf_amd_batch_trim keeps d_lines, d_pages and d_slots and releases only the
 // others -- so a set outlives a trim of its members without re-resolving anything.
-extern "C" int rf_launch_probe_fanout(void* stream, int kind, const void* in0, uint32_t key_len, uint32_t seed,
-                                      const ProbeGroup* groups, uint32_t ng, const uint32_t* member, uint32_t K,
-                                      uint64_t n, uint64_t* found);
+extern "C" int rf_launch_probe_fanout(void* stream, int kind, const void* in0, const uint64_t* offs, uint32_t key_len,
+                                      uint32_t seed, const ProbeGroup* groups, uint32_t ng, const uint32_t* member,
+                                      uint32_t K, uint64_t n, uint64_t* found);
+extern "C" void rf_fanout_set_max_blocks(uint32_t blocks);
 extern "C" uint64_t rf_found_compact_tiles(uint64_t m);
 extern "C" int rf_launch_found_compact(void* stream, const uint64_t* found, uint64_t m, uint64_t* cand, uint64_t cap,
                                        uint64_t* count, void* scratch);
@@ -2103,18 +2104,18 @@ extern "C" void rf_amd_filter_set_destroy(rf_amd_filter_set* s) {
 
 extern "C" uint32_t rf_amd_filter_set_num_members(const rf_amd_filter_set* s) { return s ? s->num_members : 0; }
 
-static int set_probe(rf_amd_filter_set* s, int kind, const void* in0, uint32_t key_len, const uint32_t* d_member,
-                     uint32_t K, uint64_t n, uint64_t* d_found, void* stream) {
+static int set_probe(rf_amd_filter_set* s, int kind, const void* in0, const uint64_t* offs, uint32_t key_len,
+                     const uint32_t* d_member, uint32_t K, uint64_t n, uint64_t* d_found, void* stream) {
   if (!s) return fail(RF_AMD_EINVAL, "null filter set");
   if (K == 0) return fail(RF_AMD_EINVAL, "K == 0");
   if (!d_member && K != s->num_members) return fail(RF_AMD_EINVAL, "all-members form: K must equal num_members");
   if (kind != IN_HASH && !s->one_seed) return fail(RF_AMD_EINVAL, "keys form over members with different seeds");
   if (n > ((1ull << 56) - 1) / K) return fail(RF_AMD_EINVAL, "n * K >= 2^56");
   if (n == 0) return 0;
-  if (!in0 || !d_found) return fail(RF_AMD_EINVAL, "null probe buffer");
+  if (!in0 || !d_found || (kind == IN_VAR && !offs)) return fail(RF_AMD_EINVAL, "null probe buffer");
   HIPCHK(hipSetDevice(s->eng->device));
   (void)hipGetLastError();
-  int rc = rf_launch_probe_fanout(stream ? stream : s->eng->stream, kind, in0, key_len, s->seed,
+  int rc = rf_launch_probe_fanout(stream ? stream : s->eng->stream, kind, in0, offs, key_len, s->seed,
                                   s->d_groups.as<ProbeGroup>(), s->num_members, d_member, K, n, d_found);
   if (rc) return fail(RF_AMD_EINVAL, std::string("fan-out probe launch: ") + hipGetErrorString((hipError_t)rc));
   return 0;
@@ -2124,11 +2125,21 @@ extern "C" int rf_amd_filter_set_probe_keys(rf_amd_filter_set* s, const void* d_
                                             const uint32_t* d_member, uint32_t K, uint64_t n, uint64_t* d_found,
                                             void* stream) {
   if (key_len == 0) return fail(RF_AMD_EINVAL, "key_len 0");
-  return set_probe(s, fixed_kind(d_keys, key_len), d_keys, key_len, d_member, K, n, d_found, stream);
+  return set_probe(s, fixed_kind(d_keys, key_len), d_keys, nullptr, key_len, d_member, K, n, d_found, stream);
+}
+extern "C" int rf_amd_filter_set_probe_var_keys(rf_amd_filter_set* s, const uint8_t* d_bytes,
+                                                const uint64_t* d_offsets, const uint32_t* d_member, uint32_t K,
+                                                uint64_t n, uint64_t* d_found, void* stream) {
+  return set_probe(s, IN_VAR, d_bytes, d_offsets, 0, d_member, K, n, d_found, stream);
 }
 extern "C" int rf_amd_filter_set_probe_hashes(rf_amd_filter_set* s, const uint32_t* d_hashes, const uint32_t* d_member,
                                               uint32_t K, uint64_t n, uint64_t* d_found, void* stream) {
-  return set_probe(s, IN_HASH, d_hashes, 4, d_member, K, n, d_found, stream);
+  return set_probe(s, IN_HASH, d_hashes, nullptr, 4, d_member, K, n, d_found, stream);
+}
+
+extern "C" int rf_amd_diag_fanout_max_blocks(uint32_t blocks) {
+  rf_fanout_set_max_blocks(blocks);
+  return 0;
 }
 
 // 8 bytes of offset and 4 of count per tile of found words, and slack to keep both aligned
@@ -2209,12 +2220,13 @@ static int upload_runs(rf_amd_batch* b, const uint64_t* h_counts, void* stream, 
   return 0;
 }
 
-static int probe_runs(rf_amd_batch* b, int kind, const void* in0, uint32_t key_len, const uint64_t* h_counts,
-                      uint64_t* d_found, void* stream) {
+static int probe_runs(rf_amd_batch* b, int kind, const void* in0, const uint64_t* offs, uint32_t key_len,
+                      const uint64_t* h_counts, uint64_t* d_found, void* stream) {
   uint64_t n = 0;
   if (int rc = upload_runs(b, h_counts, stream, &n)) return rc;
   if (n == 0) return 0;
-  return do_probe(b, kind, in0, nullptr, key_len, nullptr, n, d_found, stream, b->d_runs.as<uint64_t>());
+  if (kind == IN_VAR && !offs) return fail(RF_AMD_EINVAL, "null probe buffer");
+  return do_probe(b, kind, in0, offs, key_len, nullptr, n, d_found, stream, b->d_runs.as<uint64_t>());
 }
 
 // bench.py's measured probe floor: k_probe_floor over the same runs (rf_amd_diag.h)
@@ -2240,11 +2252,15 @@ extern "C" int rf_amd_debug_probe_floor(rf_amd_batch* b, const void* d_in, uint3
 extern "C" int rf_amd_batch_probe_keys_runs(rf_amd_batch* b, const void* d_keys, uint32_t key_len,
                                             const uint64_t* h_counts, uint64_t* d_found, void* stream) {
   if (key_len == 0) return fail(RF_AMD_EINVAL, "key_len 0");
-  return probe_runs(b, fixed_kind(d_keys, key_len), d_keys, key_len, h_counts, d_found, stream);
+  return probe_runs(b, fixed_kind(d_keys, key_len), d_keys, nullptr, key_len, h_counts, d_found, stream);
+}
+extern "C" int rf_amd_batch_probe_var_keys_runs(rf_amd_batch* b, const uint8_t* d_bytes, const uint64_t* d_offsets,
+                                                const uint64_t* h_counts, uint64_t* d_found, void* stream) {
+  return probe_runs(b, IN_VAR, d_bytes, d_offsets, 0, h_counts, d_found, stream);
 }
 extern "C" int rf_amd_batch_probe_hashes_runs(rf_amd_batch* b, const uint32_t* d_hashes, const uint64_t* h_counts,
                                               uint64_t* d_found, void* stream) {
-  return probe_runs(b, IN_HASH, d_hashes, 4, h_counts, d_found, stream);
+  return probe_runs(b, IN_HASH, d_hashes, nullptr, 4, h_counts, d_found, stream);
 }
 
 extern "C" int rf_debug_set_phase_buffer(uint64_t* d_buf, uint32_t kid);
@@ -2646,6 +2662,43 @@ extern "C" int rf_amd_filter_lookup_keys(rf_amd_engine* e, const rf_amd_config* 
         hipMemsetAsync(d_id.p, 0, 4 * n, st) != hipSuccess)
       rc = fail(RF_AMD_EINVAL, "H2D failed");
     if (!rc) rc = rf_amd_batch_probe_keys(b, d_k.p, key_len, d_id.as<uint32_t>(), n, d_f.as<uint64_t>(), st);
+    if (!rc && (hipMemcpyAsync(found_values, d_f.p, 8 * n, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                hipStreamSynchronize(st) != hipSuccess))
+      rc = fail(RF_AMD_EINVAL, "D2H failed");
+  }
+  rf_amd_batch_destroy(b);
+  return rc;
+}
+
+// only the byte range the keys occupy goes to the device, with the offsets rebased to it
+extern "C" int rf_amd_filter_lookup_var_keys(rf_amd_engine* e, const rf_amd_config* cfg, const rf_amd_image* filter,
+                                             const uint8_t* bytes, const uint64_t* offsets, uint64_t n,
+                                             uint64_t* found_values) {
+  if (!e) return fail(RF_AMD_ENODEV, "no engine");
+  if (!filter || !filter->pages) {
+    if (found_values) memset(found_values, 0, 8 * n);
+    return 0;
+  }
+  if (n == 0) return 0;
+  if (!offsets || !found_values) return fail(RF_AMD_EINVAL, "null keys");
+  const uint64_t base = offsets[0], total = offsets[n] - base;
+  if (offsets[n] < base) return fail(RF_AMD_EINVAL, "offsets decrease");
+  if (total && !bytes) return fail(RF_AMD_EINVAL, "null keys");
+  rf_amd_batch* b = nullptr;
+  if (int rc = batch_from_image(e, cfg, filter, &b)) return rc;
+  std::vector<uint64_t> rel(offsets, offsets + n + 1);
+  for (auto& o : rel) o -= base;
+  DevBuf d_k, d_o, d_f, d_id;
+  int rc = d_k.alloc(total + 16) | d_o.alloc(8 * (n + 1)) | d_f.alloc(8 * n) | d_id.alloc(4 * n);
+  if (!rc) {
+    hipStream_t st = e->stream;
+    if ((total && hipMemcpyAsync(d_k.p, bytes + base, total, hipMemcpyHostToDevice, st) != hipSuccess) ||
+        hipMemcpyAsync(d_o.p, rel.data(), 8 * (n + 1), hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemsetAsync(d_id.p, 0, 4 * n, st) != hipSuccess)
+      rc = fail(RF_AMD_EINVAL, "H2D failed");
+    if (!rc)
+      rc = rf_amd_batch_probe_var_keys(b, d_k.as<uint8_t>(), d_o.as<uint64_t>(), d_id.as<uint32_t>(), n,
+                                       d_f.as<uint64_t>(), st);
     if (!rc && (hipMemcpyAsync(found_values, d_f.p, 8 * n, hipMemcpyDeviceToHost, st) != hipSuccess ||
                 hipStreamSynchronize(st) != hipSuccess))
       rc = fail(RF_AMD_EINVAL, "D2H failed");

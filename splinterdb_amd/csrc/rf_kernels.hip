@@ -4305,7 +4305,8 @@ __global__ __launch_bounds__(WAVE) void k_probe_small(SmallProbe a) {
 // Key i is looked up in K members of a ProbeGroup table (rf_amd_filter_set_probe_*): the maplets
 // along its trunk path (trunk_merge_lookup, src/trunk.c:6008-6075), filters of any batches. A
 // wave takes 64 consecutive keys and hashes them one per lane -- each key is read and hashed
-// once, 24-byte keys staged through LDS as k_probe stages them -- and parks the hashes in LDS.
+// once, 24-byte keys staged through LDS as k_probe stages them, variable-length keys (IN_VAR:
+// bytes and n + 1 offsets) through wave_hash_var's 4 KiB window -- and parks the hashes in LDS.
 // It then walks its 64 K (key, slot) pairs in row-major order, 64 per step: lane p of a step
 // handles key p / K, slot p % K, so member ids are read and found words stored coalesced
 // (non-temporal, as k_probe's). FAN_U steps go together: their member ids, then their group
@@ -4318,15 +4319,23 @@ constexpr int FAN_NT = 256;
 #define RF_FAN_U 2
 #endif
 constexpr int FAN_U = RF_FAN_U;  // steps whose loads are in flight together
+#ifndef RF_FAN_VCAP
+#define RF_FAN_VCAP 4096
+#endif
+constexpr uint32_t FAN_VCAP = RF_FAN_VCAP;  // IN_VAR: the key window's bytes (k_probe's and k_hash's size)
 
 template <int KIND>
-__global__ __launch_bounds__(FAN_NT) void k_probe_fanout(const void* __restrict__ in0, uint32_t key_len,
+__global__ __launch_bounds__(FAN_NT) void k_probe_fanout(const void* __restrict__ in0,
+                                                         const uint64_t* __restrict__ offs, uint32_t key_len,
                                                          uint32_t seed, const ProbeGroup* __restrict__ groups,
                                                          uint32_t ng, const uint32_t* __restrict__ member,
                                                          uint32_t K, uint64_t n, uint64_t* __restrict__ found) {
   constexpr bool WAVE_KEYS = KIND == IN_KEYS24;
+  constexpr bool WAVE_VAR = KIND == IN_VAR;
   constexpr int NW = FAN_NT / WAVE;
   __shared__ v4u s_keys[NW][WAVE_KEYS ? 96 : 1];
+  constexpr uint32_t VCAP = FAN_VCAP;
+  __shared__ __attribute__((aligned(16))) uint32_t s_vk[WAVE_VAR ? NW : 1][WAVE_VAR ? VCAP / 4 + 4 : 1];
   __shared__ uint32_t s_h[NW][WAVE];
   const uint32_t lane = threadIdx.x & (WAVE - 1);
   const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x) / WAVE;
@@ -4369,6 +4378,18 @@ __global__ __launch_bounds__(FAN_NT) void k_probe_fanout(const void* __restrict_
       } else if (lane < nk) {
         h = hash_key<KIND, true>(in0, nullptr, key_len, seed, wf + lane);
       }
+    } else if constexpr (WAVE_VAR) {
+      // variable-length keys: the wave's 64 keys are one contiguous byte range, staged in a
+      // 4 KiB LDS window and hashed from there (wave_hash_var: ballots and wave barriers, so
+      // every lane calls it). The window state starts empty for every chunk.
+      uint64_t o0 = 0, o1 = 0;
+      if (lane < nk) {
+        o0 = offs[wf + lane];
+        o1 = offs[wf + lane + 1];
+      }
+      uint64_t win0 = 0, win1 = 0;
+      h = wave_hash_var<VCAP, true>(static_cast<const uint8_t*>(in0), o0, o1, lane < nk, s_vk[wv], seed, &win0,
+                                    &win1);
     } else {
       if (lane < nk) h = hash_key<KIND, true>(in0, nullptr, key_len, seed, wf + lane);
     }
@@ -4443,7 +4464,7 @@ __global__ __launch_bounds__(FAN_NT) void k_probe_fanout(const void* __restrict_
         if (kk[u] < nk) __builtin_nontemporal_store(r, found + pbase + p0 + (uint64_t)u * WAVE);
       }
     }
-    wave_sync_lds();  // the next chunk's keys and hashes overwrite this one's
+    wave_sync_lds();  // the next chunk's keys, key window and hashes overwrite this one's
   }
 }
 
@@ -4548,18 +4569,31 @@ extern "C" int rf_launch_found_compact(void* stream, const uint64_t* found, uint
   return e == hipSuccess ? 0 : (int)e;
 }
 
-extern "C" int rf_launch_probe_fanout(void* stream, int kind, const void* in0, uint32_t key_len, uint32_t seed,
-                                      const ProbeGroup* groups, uint32_t ng, const uint32_t* member, uint32_t K,
-                                      uint64_t n, uint64_t* found) {
+// diagnostics (rf_amd_diag_fanout_max_blocks): a cap on the grid below, so that a small probe
+// runs several chunks per wave; 0 = none
+static std::atomic<uint32_t> g_fanout_max_blocks{0};
+extern "C" void rf_fanout_set_max_blocks(uint32_t blocks) {
+  g_fanout_max_blocks.store(blocks, std::memory_order_relaxed);
+}
+
+// offs: the n + 1 byte offsets of IN_VAR keys (in0 = their bytes), unused by the other kinds
+extern "C" int rf_launch_probe_fanout(void* stream, int kind, const void* in0, const uint64_t* offs, uint32_t key_len,
+                                      uint32_t seed, const ProbeGroup* groups, uint32_t ng, const uint32_t* member,
+                                      uint32_t K, uint64_t n, uint64_t* found) {
   if (n == 0) return 0;
-  const uint64_t nblk = ((n + WAVE - 1) / WAVE + FAN_NT / WAVE - 1) / (FAN_NT / WAVE);
-  const dim3 g((uint32_t)(nblk < 0x7fffffffull ? nblk : 0x7fffffffull)), b(FAN_NT);
-#define L(KD) hipLaunchKernelGGL((k_probe_fanout<KD>), g, b, 0, (hipStream_t)stream, in0, key_len, seed, groups, ng, member, K, n, found)
+  uint64_t nblk = ((n + WAVE - 1) / WAVE + FAN_NT / WAVE - 1) / (FAN_NT / WAVE);
+  if (nblk > 0x7fffffffull) nblk = 0x7fffffffull;
+  const uint32_t cap = g_fanout_max_blocks.load(std::memory_order_relaxed);
+  if (cap && nblk > cap) nblk = cap;
+  const dim3 g((uint32_t)nblk), b(FAN_NT);
+#define L(KD) hipLaunchKernelGGL((k_probe_fanout<KD>), g, b, 0, (hipStream_t)stream, in0, offs, key_len, seed, groups, ng, member, K, n, found)
   switch (kind) {
     case IN_KEYS24: L(IN_KEYS24); break;
     case IN_KEYS_W: L(IN_KEYS_W); break;
     case IN_KEYS_B: L(IN_KEYS_B); break;
-    default: L(IN_HASH); break;
+    case IN_VAR: L(IN_VAR); break;
+    case IN_HASH: L(IN_HASH); break;
+    default: return (int)hipErrorInvalidValue;
   }
 #undef L
   const hipError_t e = hipGetLastError();

@@ -60,6 +60,8 @@ EXPORTED = [
     "rf_amd_filter_set_create", "rf_amd_filter_set_destroy", "rf_amd_filter_set_num_members",
     "rf_amd_filter_set_probe_keys", "rf_amd_filter_set_probe_hashes",
     "rf_amd_found_compact_scratch_bytes", "rf_amd_found_compact",
+    "rf_amd_filter_set_probe_var_keys", "rf_amd_batch_probe_var_keys_runs", "rf_amd_filter_lookup_var_keys",
+    "rf_amd_diag_fanout_max_blocks",
 ]
 ROUTE_MAX_WORLD = 16
 FOUND_COMPACT_TILE = 4096  # found words per workgroup of rf_amd_found_compact (FC_TILE)
@@ -237,6 +239,11 @@ def load_library(build_if_missing=True):
     L.rf_amd_found_compact_scratch_bytes.argtypes = [u64]
     L.rf_amd_found_compact_scratch_bytes.restype = u64
     L.rf_amd_found_compact.argtypes = [vp, vp, u64, vp, u64, vp, vp, vp]
+    L.rf_amd_filter_set_probe_var_keys.argtypes = [vp, vp, vp, vp, u32, u64, vp, vp]
+    L.rf_amd_batch_probe_var_keys_runs.argtypes = [vp, vp, vp, ctypes.POINTER(u64), vp, vp]
+    L.rf_amd_filter_lookup_var_keys.argtypes = [vp, ctypes.POINTER(RfConfig), ctypes.POINTER(RfImage),
+                                                vp, vp, u64, vp]
+    L.rf_amd_diag_fanout_max_blocks.argtypes = [u32]
     _lib = L
     return L
 
@@ -419,6 +426,22 @@ def routing_filter_lookup_keys(cfg: RoutingConfig, filt, keys: np.ndarray, engin
     _check(L.rf_amd_filter_lookup_keys(eng.h, ctypes.byref(cfg.c()),
                                        ctypes.byref(fc) if fc is not None else None,
                                        k.ctypes.data, k.shape[1], k.shape[0], out.ctypes.data))
+    return out
+
+
+def routing_filter_lookup_var_keys(cfg: RoutingConfig, filt, data, offs, engine=None):
+    """Variable-length keys in host memory, key i = data[offs[i]:offs[i+1]] (n + 1 offsets),
+    hashed and probed on the GPU; only data[offs[0]:offs[n]] is copied in."""
+    eng = engine or default_engine()
+    L = load_library()
+    d = np.ascontiguousarray(data, dtype=np.uint8)
+    o = np.ascontiguousarray(offs, dtype=np.uint64)
+    n = max(o.size - 1, 0)
+    out = np.zeros(n, dtype=np.uint64)
+    fc = filt._c() if filt is not None else None
+    _check(L.rf_amd_filter_lookup_var_keys(eng.h, ctypes.byref(cfg.c()),
+                                           ctypes.byref(fc) if fc is not None else None,
+                                           d.ctypes.data, o.ctypes.data, n, out.ctypes.data))
     return out
 
 
@@ -789,6 +812,12 @@ class FilterBatch:
         _check(load_library().rf_amd_batch_probe_hashes_runs(self.h, _dptr(d_hashes), c, _dptr(d_found),
                                                              _stream(stream)))
 
+    def probe_var_keys_runs(self, d_bytes, d_offsets, counts, d_found, stream=None):
+        """probe_keys_runs for variable-length keys (bytes and sum(counts) + 1 offsets)"""
+        c = (ctypes.c_uint64 * self.F)(*[int(x) for x in counts])
+        _check(load_library().rf_amd_batch_probe_var_keys_runs(self.h, _dptr(d_bytes), _dptr(d_offsets), c,
+                                                               _dptr(d_found), _stream(stream)))
+
     def probe_floor(self, d_in, key_len, counts, d_out, stream=None):
         """The probe's memory floor (rf_amd_debug_probe_floor): the fast path's traffic over the
         same runs with the arithmetic removed; d_out gets no lookup results."""
@@ -901,6 +930,12 @@ def found_compact(d_found, m, d_cand, d_count, stream=None, engine=None):
     _compact_scratch[(id(eng), st)] = scratch
 
 
+def diag_fanout_max_blocks(blocks: int):
+    """rf_amd_diag_fanout_max_blocks: cap the fan-out probe's grid (diagnostics, process-wide)
+    so that every wave takes several 64-key chunks; 0 restores the default"""
+    _check(load_library().rf_amd_diag_fanout_max_blocks(int(blocks)))
+
+
 class FilterSet:
     """A resident table of filters of any batches (rf_amd_filter_set): members = [(FilterBatch,
     index) or None]. The member batches must outlive the set's last probe."""
@@ -942,15 +977,34 @@ class FilterSet:
         _check(load_library().rf_amd_filter_set_probe_hashes(self.h, _dptr(d_hashes), _dptr(d_member), K, n,
                                                              _dptr(d_found), _stream(stream)))
 
+    def probe_var_keys(self, d_bytes, d_offsets, d_member, K, n, d_found, stream=None):
+        """probe_keys for variable-length keys: key i is d_bytes[d_offsets[i] : d_offsets[i+1]]
+        (n + 1 uint64 byte offsets)"""
+        _check(load_library().rf_amd_filter_set_probe_var_keys(self.h, _dptr(d_bytes), _dptr(d_offsets),
+                                                               _dptr(d_member), K, n, _dptr(d_found),
+                                                               _stream(stream)))
+
     def multiget(self, d_keys, key_len, d_member, K, n, cap=None, stream=None):
         """probe_keys + found_compact: returns (d_cand, count), the first `count` records of
         d_cand being the candidates key * K + slot << 8 | value in order. One synchronisation;
         a second compaction and synchronisation when the candidates outnumber `cap` (default:
         one per key)."""
         import torch
-        dev = d_keys.device
-        d_found = torch.empty(n * K, dtype=torch.int64, device=dev)
+        d_found = torch.empty(n * K, dtype=torch.int64, device=d_keys.device)
         self.probe_keys(d_keys, key_len, d_member, K, n, d_found, stream)
+        return self._compact_found(d_found, n, K, cap, stream)
+
+    def multiget_var(self, d_bytes, d_offsets, d_member, K, n, cap=None, stream=None):
+        """multiget for variable-length keys (probe_var_keys + found_compact)"""
+        import torch
+        d_found = torch.empty(n * K, dtype=torch.int64, device=d_offsets.device)
+        self.probe_var_keys(d_bytes, d_offsets, d_member, K, n, d_found, stream)
+        return self._compact_found(d_found, n, K, cap, stream)
+
+    def _compact_found(self, d_found, n, K, cap, stream):
+        """the multi-get's tail: the candidates of d_found[:n * K] as (d_cand, count)"""
+        import torch
+        dev = d_found.device
         d_count = torch.zeros(1, dtype=torch.int64, device=dev)
         d_cand = torch.empty(max(1, n) if cap is None else cap, dtype=torch.int64, device=dev)
         def read_count():

@@ -12,8 +12,14 @@ whether the ranges touch, the compaction's time (rf_amd_found_compact at cap = c
 bytes of the dense n K words against those of the candidate list, and the time of each one's
 copy into pinned host memory. Both ways' words are compared before anything is reported.
 
-    timeout -k 10 600 python tools/multiget.py [--filters 64] [--keys 1048576] [--n 16777216]
-                                               [--k 4] [--rounds 7] [--warmup 2]
+--var: the same two ways on variable-length keys (keys.var_keys: 8-100 B, C5's distribution,
+generated on the host): FilterSet.probe_var_keys against hash_var_keys + repeat_interleave +
+probe_hashes. Key i is a member of filter i % 64: each filter is built (build_hashes) from the
+hashes of its n / 64 probe keys and random hashes up to its 2^20. Default output:
+profiles/multiget_var.json.
+
+    timeout -k 10 600 python tools/multiget.py [--var] [--filters 64] [--keys 1048576]
+                                               [--n 16777216] [--k 4] [--rounds 7] [--warmup 2]
                                                [--out profiles/multiget.json]
 """
 import argparse
@@ -39,8 +45,11 @@ def main():
     ap.add_argument("--k", type=int, default=4)
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "multiget.json"))
+    ap.add_argument("--var", action="store_true", help="variable-length keys (8-100 B)")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "multiget_var.json" if args.var else "multiget.json")
     if not torch.cuda.is_available():
         sys.exit("multiget.py measures on the GPU: no HIP device")
     F, nk, n, Kf = args.filters, args.keys, args.n, args.k
@@ -50,33 +59,57 @@ def main():
     eng = E.Engine(0)
     stream = torch.cuda.Stream(device=dev)
     st = stream.cuda_stream
+    mean_len = 24.0
+    if args.var:
+        assert n % F == 0 and n // F <= nk, "--var: n a multiple of the filters, at most keys-per-filter each"
+        vdata, voffs = K.var_keys(n)
+        mean_len = float(voffs[-1]) / n
     with torch.cuda.stream(stream):
-        gid = torch.arange(F, device=dev, dtype=torch.int64)[:, None] << 32
-        j = torch.arange(nk, device=dev, dtype=torch.int64)[None, :]
-        batch = E.FilterBatch(cfg, [nk] * F, list(range(F)), engine=eng)  # filter f tags its keys with value f
-        batch.build_keys(K.ids_keys_torch((gid + j).reshape(-1), 24), 24, stream=st)
-        batch.infos(stream=st)
-        del gid, j
         g = torch.Generator(device=dev)
         g.manual_seed(7)
         i = torch.arange(n, device=dev, dtype=torch.int64)
         own = i % F
-        ids = (own << 32) + torch.randint(0, nk, (n,), device=dev, generator=g)
-        keys = K.ids_keys_torch(ids, 24)
+        hashes = torch.zeros(n, dtype=torch.int32, device=dev)
+        batch = E.FilterBatch(cfg, [nk] * F, list(range(F)), engine=eng)  # filter f tags its keys with value f
+        if args.var:
+            d_bytes = torch.from_numpy(vdata).to(dev)
+            d_offs = torch.from_numpy(voffs.view("int64")).to(dev)
+            del vdata, voffs
+            E.hash_var_keys(cfg, d_bytes, d_offs, n, hashes, stream=st, engine=eng)
+            fill = torch.randint(-(1 << 31), 1 << 31, (F, nk), device=dev, generator=g).to(torch.int32)
+            fill[:, :n // F] = hashes.view(n // F, F).t()  # filter f: the keys with i % F == f
+            batch.build_hashes(fill.contiguous(), stream=st)
+            batch.infos(stream=st)
+            del fill
+        else:
+            gid = torch.arange(F, device=dev, dtype=torch.int64)[:, None] << 32
+            j = torch.arange(nk, device=dev, dtype=torch.int64)[None, :]
+            batch.build_keys(K.ids_keys_torch((gid + j).reshape(-1), 24), 24, stream=st)
+            batch.infos(stream=st)
+            del gid, j
+            ids = (own << 32) + torch.randint(0, nk, (n,), device=dev, generator=g)
+            keys = K.ids_keys_torch(ids, 24)
+            del ids
         member = torch.randint(0, F, (n, Kf), device=dev, generator=g).to(torch.int32).contiguous()
-        del i, ids
+        del i
         fset = E.FilterSet([(batch, f) for f in range(F)], engine=eng)
         found_a = torch.zeros(n * Kf, dtype=torch.int64, device=dev)
         found_b = torch.zeros(n * Kf, dtype=torch.int64, device=dev)
-        hashes = torch.zeros(n, dtype=torch.int32, device=dev)
+        hashes.zero_()
         d_count = torch.zeros(1, dtype=torch.int64, device=dev)
     stream.synchronize()
 
     def fanout():
-        fset.probe_keys(keys, 24, member, Kf, n, found_a, stream=st)
+        if args.var:
+            fset.probe_var_keys(d_bytes, d_offs, member, Kf, n, found_a, stream=st)
+        else:
+            fset.probe_keys(keys, 24, member, Kf, n, found_a, stream=st)
 
     def replicate():
-        E.hash_keys(cfg, keys, 24, n, hashes, stream=st, engine=eng)
+        if args.var:
+            E.hash_var_keys(cfg, d_bytes, d_offs, n, hashes, stream=st, engine=eng)
+        else:
+            E.hash_keys(cfg, keys, 24, n, hashes, stream=st, engine=eng)
         rep = torch.repeat_interleave(hashes, Kf)
         batch.probe_hashes(rep, member, n * Kf, found_b, stream=st)
 
@@ -128,18 +161,27 @@ def main():
         return {"min": round(min(v), 4), "max": round(max(v), 4), "rounds": [round(x, 4) for x in v]}
 
     fa, rb = t["fanout"], t["replicate"]
+    what = ("multi-get of n 24-byte keys, K random members per key, one batch of F filters: "
+            "FilterSet.probe_keys against hash_keys + repeat_interleave + probe_hashes with per-probe "
+            "filter ids; alternating rounds in one process, HIP events on the launch stream")
+    config = {"filters": F, "keys_per_filter": nk, "n": n, "K": Kf, "rounds": args.rounds,
+              "warmup": args.warmup, "fingerprint_size": 26, "log_index_size": 8}
+    if args.var:
+        what = ("multi-get of n variable-length keys (keys.var_keys, 8-100 B), K random members per key, one "
+                "batch of F filters: FilterSet.probe_var_keys against hash_var_keys + repeat_interleave + "
+                "probe_hashes with per-probe filter ids; alternating rounds in one process, HIP events on the "
+                "launch stream")
+        config["mean_key_len"] = round(mean_len, 3)
     out = {
-        "what": "multi-get of n 24-byte keys, K random members per key, one batch of F filters: "
-                "FilterSet.probe_keys against hash_keys + repeat_interleave + probe_hashes with per-probe "
-                "filter ids; alternating rounds in one process, HIP events on the launch stream",
-        "config": {"filters": F, "keys_per_filter": nk, "n": n, "K": Kf, "rounds": args.rounds,
-                   "warmup": args.warmup, "fingerprint_size": 26, "log_index_size": 8},
+        "what": what,
+        "config": config,
         "fanout_ms": rng(fa),
         "replicate_ms": rng(rb),
         "ranges_touch": not (max(fa) < min(rb) or max(rb) < min(fa)),
         "fanout_faster_beyond_ranges": bool(max(fa) < min(rb)),
         "fanout_slower_beyond_ranges": bool(max(rb) < min(fa)),
-        "fanout_algorithmic_bytes_per_key": 24 + Kf * (4 + 64 + 8),
+        # the key (--var: its mean length and 8 bytes of offset), then per member an id, a line, a word
+        "fanout_algorithmic_bytes_per_key": (round(mean_len + 8, 3) if args.var else 24) + Kf * (4 + 64 + 8),
         "compact_ms": rng(t_compact),
         "candidates": count,
         "dense_bytes": n * Kf * 8,
