@@ -26,23 +26,9 @@
 #include "../../include/rf_amd_diag.h"
 #include "rf_plan.h"
 #include "rf_batch_plan.h"
+#include "rf_launch.h"
 
 using namespace rf;
-
-extern "C" int rf_launch_build(const LaunchArgs* a);
-extern "C" int rf_launch_place(void* stream, const uint8_t* img, const uint64_t* slots, uint32_t first_page,
-                                uint32_t count, uint32_t num_pages, uint32_t num_indices, uint32_t page_size,
-                                const uint64_t* table, uint32_t addrs_per_page);
-extern "C" int rf_launch_old_decode(const LaunchArgs* a);
-extern "C" int rf_launch_wave_tab(void* stream, const uint64_t* runs, uint32_t nf, uint64_t n, uint32_t* tab);
-extern "C" int rf_launch_plines(const LaunchArgs* a);
-extern "C" int rf_launch_seg_fill(void* stream, const uint32_t* pre, uint32_t nf, uint32_t n, uint32_t* fof,
-                                  uint32_t* start, uint32_t mul);
-extern "C" int rf_launch_build_init(void* stream, uint32_t* cb_count, uint32_t* cb_cursor, uint32_t num_cb,
-                                    uint32_t* outs_words, uint32_t num_out_words, uint32_t* overflow,
-                                    uint32_t* spill, uint32_t* plist);
-extern "C" int rf_launch_probe(const LaunchArgs* a, int kind, const void* in0, const uint64_t* offs,
-                               uint32_t key_len, const uint32_t* filter_id, uint64_t n, uint64_t* found);
 
 static thread_local std::string g_err;
 static int fail(int rc, const std::string& msg) {
@@ -1171,11 +1157,6 @@ extern "C" int rf_amd_batch_build_hashes_host(rf_amd_batch* b, const uint32_t* h
 }
 
 // ---- host-buffer lookups over the engine's lookup slots (ProbeSlot) -----------------------
-extern "C" int rf_launch_probe_groups(void* stream, const uint32_t* in, const ProbeGroup* groups, uint32_t ng,
-                                      uint64_t n, uint64_t* found, uint32_t* counter, uint32_t* done_flag,
-                                      uint32_t seq);
-extern "C" int rf_launch_probe_small(void* stream, const SmallProbe* a);
-
 static ProbeSlot* slot_take(rf_amd_engine* e) {
   {
     std::lock_guard<std::mutex> g(e->slot_mu);
@@ -1304,8 +1285,6 @@ static int slot_wait(ProbeSlot* s, uint32_t seq, bool sync) {
 }
 
 // ---- the lookup server (host side) --------------------------------------------------------
-extern "C" int rf_launch_lookup_server(void* stream, const SrvReq* ring, SrvRes* res, SrvCtl* ctl, uint64_t head,
-                                       uint64_t gen, uint64_t idle_ticks, uint64_t life_ticks);
 static const uint64_t SRV_UNPUBLISHED = ~0ull, SRV_BUSY = ~0ull - 1;
 static_assert(SRV_RING == RF_AMD_SERVER_RING, "rf_amd.h and the kernels agree on the ring size");
 
@@ -1503,52 +1482,14 @@ static int srv_dead(rf_amd_engine* e) {
 static ProbeGroup probe_group_of(const rf_amd_batch* b, uint32_t f);
 static int batch_errors(rf_amd_batch* b);
 
-// RF_AMD_REAP_TAIL=1: the reap loop bounded by the ticket counter (A/B switch; by default the
-// answers' checks bound it and the submitters' counter line is not read)
-static bool srv_reap_tail() {
-  static const bool on = [] {
-    const char* s = getenv("RF_AMD_REAP_TAIL");
-    return s && atoi(s) > 0;
-  }();
-  return on;
-}
 // the request's 16 words (payload | check << 32) into its slot. Each 8-byte word is valid on
-// its own, so wider stores are as safe as 8-byte ones: RF_AMD_SRV_STORE = 8 (eight-byte
-// stores), 16 (SSE, the default) or 32 (AVX) -- an A/B switch
-static int srv_store_width() {
-  static const int w = [] {
-    const char* s = getenv("RF_AMD_SRV_STORE");
-    const int v = s ? atoi(s) : 16;
-    return v == 8 || v == 32 ? v : 16;
-  }();
-  return w;
-}
-__attribute__((target("avx2"))) static void srv_write_request_avx(uint64_t* dst, const uint64_t* src) {
-  for (uint32_t k = 0; k < SRV_REQ_WORDS; k += 4)
-    _mm256_store_si256(reinterpret_cast<__m256i*>(dst + k), _mm256_loadu_si256(reinterpret_cast<const __m256i*>(src + k)));
-}
+// its own, so 16-byte (SSE) stores are as safe as 8-byte ones; no sfence after a request
+// (whole lines leave the write-combining buffers without one)
 static inline void srv_write_request(uint64_t* dst, const uint32_t* p, uint64_t ck) {
-  alignas(32) uint64_t w[SRV_REQ_WORDS];
+  alignas(16) uint64_t w[SRV_REQ_WORDS];
   for (uint32_t k = 0; k < SRV_REQ_WORDS; k++) w[k] = (uint64_t)p[k] | ck;
-  const int width = srv_store_width();
-  if (width == 8) {
-    volatile uint64_t* d = dst;
-    for (uint32_t k = 0; k < SRV_REQ_WORDS; k++) d[k] = w[k];
-  } else if (width == 16) {
-    for (uint32_t k = 0; k < SRV_REQ_WORDS; k += 2)
-      _mm_store_si128(reinterpret_cast<__m128i*>(dst + k), _mm_load_si128(reinterpret_cast<const __m128i*>(w + k)));
-  } else {
-    srv_write_request_avx(dst, w);
-  }
-}
-// RF_AMD_SRV_SFENCE=1: an sfence after each request (A/B switch: whole lines leave the
-// write-combining buffers without one)
-static bool srv_sfence() {
-  static const bool on = [] {
-    const char* s = getenv("RF_AMD_SRV_SFENCE");
-    return s && atoi(s) > 0;
-  }();
-  return on;
+  for (uint32_t k = 0; k < SRV_REQ_WORDS; k += 2)
+    _mm_store_si128(reinterpret_cast<__m128i*>(dst + k), _mm_load_si128(reinterpret_cast<const __m128i*>(w + k)));
 }
 
 // RF_AMD_SUBMIT_PROFILE=1 (diagnostics): TSC cycles of the steps of rf_amd_lookup_submit --
@@ -1669,7 +1610,6 @@ extern "C" int rf_amd_lookup_submit(rf_amd_engine* e, rf_amd_batch* b, uint32_t 
     v.meta[slot].ticket.store(t, std::memory_order_release);
     const uint64_t ck = (uint64_t)srv_check(t) << 32;
     srv_write_request(v.ring[slot].w, p, ck);
-    if (srv_sfence()) _mm_sfence();
   }
   *ticket = t;
   const uint64_t c3 = g_subprof > 0 ? tsc_ser() : 0;
@@ -1742,10 +1682,9 @@ extern "C" uint64_t rf_amd_lookup_reap(rf_amd_engine* e, void** tags, uint64_t* 
   // done when its answer is there (a waiter's, tag 0, is left to its waiter), when its slot
   // already holds a later answer (a waiter took t and the slot was reused), or when it was
   // abandoned unpublished.
-  const uint64_t tail = srv_reap_tail() ? v.tail.load(std::memory_order_acquire) : ~0ull;
   const uint64_t r2 = prof ? __rdtsc() : 0;
-  for (uint64_t q = t; q < tail && q < t + 16; q += 2) __builtin_prefetch(&v.res[q & (SRV_RING - 1)], 0, 0);
-  while (n < max && t < tail) {
+  for (uint64_t q = t; q < t + 16; q += 2) __builtin_prefetch(&v.res[q & (SRV_RING - 1)], 0, 0);
+  while (n < max) {
     const uint32_t slot = (uint32_t)(t & (SRV_RING - 1));
     if ((t & 1) == 0) __builtin_prefetch(&v.res[(t + 16) & (SRV_RING - 1)], 0, 0);
     uint64_t found = 0, tag = 0;
@@ -1890,7 +1829,6 @@ struct LookupClock {
 #endif
 extern "C" const char* rf_amd_build_id(void) { return RF_AMD_SRC_ID; }
 
-extern "C" uint64_t rf_k4_bitmap_builds(void);  // rf_kernels.hip: counted where K4 is launched
 extern "C" uint64_t rf_amd_diag_k4_bitmap_builds(void) { return rf_k4_bitmap_builds(); }
 
 extern "C" int rf_amd_diag_lookup_stats(uint64_t* out, int reset) {
@@ -2039,14 +1977,6 @@ extern "C" int rf_amd_probe_many_hashes_host(rf_amd_engine* e, rf_amd_batch* con
 // g's probe lines, pages and slots by address. Those buffers stay where they are for the
 // batch's lifetime -- rf_amd_batch_trim keeps d_lines, d_pages and d_slots and releases only the
 // others -- so a set outlives a trim of its members without re-resolving anything.
-extern "C" int rf_launch_probe_fanout(void* stream, int kind, const void* in0, const uint64_t* offs, uint32_t key_len,
-                                      uint32_t seed, const ProbeGroup* groups, uint32_t ng, const uint32_t* member,
-                                      uint32_t K, uint64_t n, uint64_t* found);
-extern "C" void rf_fanout_set_max_blocks(uint32_t blocks);
-extern "C" uint64_t rf_found_compact_tiles(uint64_t m);
-extern "C" int rf_launch_found_compact(void* stream, const uint64_t* found, uint64_t m, uint64_t* cand, uint64_t cap,
-                                       uint64_t* count, void* scratch);
-
 struct rf_amd_filter_set {
   rf_amd_engine* eng = nullptr;
   uint32_t num_members = 0;
@@ -2230,7 +2160,6 @@ static int probe_runs(rf_amd_batch* b, int kind, const void* in0, const uint64_t
 }
 
 // bench.py's measured probe floor: k_probe_floor over the same runs (rf_amd_diag.h)
-extern "C" int rf_launch_probe_floor(const LaunchArgs* pa, int kind, const void* in0, uint64_t n, uint64_t* found);
 extern "C" int rf_amd_debug_probe_floor(rf_amd_batch* b, const void* d_in, uint32_t key_len, const uint64_t* h_counts,
                                         uint64_t* d_out, void* stream) {
   if (key_len != 24 && key_len != 4) return fail(RF_AMD_EINVAL, "probe floor: 24-byte keys or 4-byte hashes");
@@ -2263,7 +2192,6 @@ extern "C" int rf_amd_batch_probe_hashes_runs(rf_amd_batch* b, const uint32_t* d
   return probe_runs(b, IN_HASH, d_hashes, nullptr, 4, h_counts, d_found, stream);
 }
 
-extern "C" int rf_debug_set_phase_buffer(uint64_t* d_buf, uint32_t kid);
 extern "C" int rf_amd_debug_phase_buffer(void* d_buf, uint32_t kernel) {
 #ifdef RF_PHASE_STAMPS
   return rf_debug_set_phase_buffer(static_cast<uint64_t*>(d_buf), kernel) ? fail(RF_AMD_EINVAL, "phase buffer") : 0;
@@ -2741,8 +2669,6 @@ extern "C" uint64_t rf_amd_space_use_bytes(const rf_amd_config* cfg, uint32_t nu
 }
 
 // ---- routing_filter_estimate_unique_fp (src/routing_filter.c:702-848) --------------------
-extern "C" int rf_launch_estimate(void* stream, const EstFilter* fl, uint32_t num_filters, uint32_t total_idx,
-                                  uint32_t lis, uint32_t* bitmap, uint64_t bitmap_words, uint32_t* counters);
 constexpr uint64_t EST_MAX_FILTERS = 32;  // MAX_FILTERS, src/routing_filter.h:25
 
 // fl: the filters to decode (pages/slots already device pointers, idx_first unset);
@@ -2973,9 +2899,6 @@ extern "C" void rf_amd_lookup_async_free(rf_amd_lookup_async_state* s) {
 }
 
 // ---- batch hashing (data_key_hash, btree_pack's fingerprint loop) -------------------------
-extern "C" int rf_launch_hash(void* stream, int kind, const void* in0, const uint64_t* offs, uint32_t key_len,
-                              uint32_t seed, uint64_t n, uint32_t* out);
-
 extern "C" int rf_amd_hash_keys(rf_amd_engine* e, const rf_amd_config* cfg, const void* d_keys, uint32_t key_len,
                                 uint64_t n, uint32_t* d_hashes, void* stream) {
   if (!e) return fail(RF_AMD_ENODEV, "no engine");
@@ -3000,13 +2923,6 @@ extern "C" int rf_amd_hash_var_keys(rf_amd_engine* e, const rf_amd_config* cfg, 
 }
 
 // ---- routed probes across ranks --------------------------------------------
-extern "C" uint64_t rf_route_scratch_words(uint64_t n, uint32_t world);
-extern "C" int rf_launch_route(void* stream, const uint32_t* hashes, const uint32_t* gfid, uint64_t n,
-                               const uint32_t* route, uint32_t num_g, uint32_t world, uint64_t* pairs,
-                               uint32_t* perm, uint32_t* scratch, uint64_t* totals);
-extern "C" int rf_launch_unroute(void* stream, const uint64_t* back, const uint32_t* perm, uint64_t n,
-                                 uint64_t* found);
-
 extern "C" uint64_t rf_amd_route_scratch_bytes(uint64_t n, uint32_t world) {
   return 4 * rf_route_scratch_words(n, world) + 8 + 8 * (uint64_t)RF_AMD_ROUTE_MAX_WORLD;
 }
@@ -3055,9 +2971,6 @@ extern "C" int rf_amd_batch_probe_pairs(rf_amd_batch* b, const uint64_t* d_pairs
 }
 
 // ---- routing_filter_verify (src/routing_filter.c:1163-1183) ------------------------------
-extern "C" int rf_launch_count_missing(void* stream, const uint64_t* found, uint64_t n, uint32_t value,
-                                       unsigned long long* missing);
-
 extern "C" int rf_amd_filter_verify(rf_amd_engine* e, const rf_amd_config* cfg, const rf_amd_image* filter,
                                     const void* keys, uint32_t key_len, uint64_t n, uint16_t value,
                                     uint64_t* num_missing) {

@@ -36,6 +36,7 @@
 
 #include "rf_device.h"
 #include "rf_plan.h"
+#include "rf_launch.h"
 
 using namespace rf;
 
@@ -76,6 +77,20 @@ __device__ __forceinline__ uint32_t hash_key(const void* __restrict__ in0, const
     else return static_cast<const uint32_t*>(in0)[k];
   }
 }
+
+// dispatch on the input kind (template parameter of the hashing kernels): the key kinds' arms
+// of a switch, for launchers with arms of their own, and the usual switch (anything else is
+// hashes)
+#define KEY_KIND_CASES(L)              \
+  case IN_KEYS24: L(IN_KEYS24); break; \
+  case IN_KEYS_W: L(IN_KEYS_W); break; \
+  case IN_KEYS_B: L(IN_KEYS_B); break; \
+  case IN_VAR: L(IN_VAR); break;
+#define KIND_SWITCH(kind, L)    \
+  switch (kind) {               \
+    KEY_KIND_CASES(L)           \
+    default: L(IN_HASH); break; \
+  }
 
 // position of the r-th (0-based) set bit of x (exists)
 __device__ __forceinline__ uint32_t select64_fast(uint64_t x, uint32_t r) {
@@ -396,9 +411,6 @@ extern "C" int rf_debug_set_phase_buffer(uint64_t* d_buf, uint32_t kid) {
 #ifndef RF_SCAT_WPE
 #define RF_SCAT_WPE 4
 #endif
-#ifndef RF_SCAT_X3
-#define RF_SCAT_X3 1
-#endif
 // FL (32-bit incremental builds): the entries are written flagged new, (e << 1) | 1.
 // RUNS (chained batches): the tile's value and end come from its run (TileRuns).
 template <int KIND, bool FL = false, bool RUNS = false>
@@ -441,7 +453,7 @@ __global__ __launch_bounds__(SCAT_NT) __attribute__((amdgpu_waves_per_eu(RF_SCAT
   // for variable-length keys, where a wave takes 64 * PER consecutive keys (one byte stream)
   // 24-byte keys (X3): a wave's 64 keys of slot k are one 1,536-byte range, read as two
   // contiguous 768-byte dwordx3 loads; lane 2i holds key i, lane 2i + 1 key 32 + i
-  constexpr bool X3 = KIND == IN_KEYS24 && RF_SCAT_X3;
+  constexpr bool X3 = KIND == IN_KEYS24;
   const uint32_t lane = threadIdx.x & (WAVE - 1);
   auto key_of = [&](int k) -> uint32_t {
     if constexpr (KIND == IN_VAR) return (threadIdx.x & ~(WAVE - 1)) * PER + k * WAVE + lane;
@@ -3167,10 +3179,8 @@ extern "C" int rf_launch_hash(void* stream, int kind, const void* in0, const uin
   if (n == 0) return 0;
   const dim3 g((uint32_t)((n + 255) / 256)), b(256);
 #define L(K) hipLaunchKernelGGL((k_hash<K>), g, b, 0, (hipStream_t)stream, in0, offs, key_len, seed, n, out)
-  switch (kind) {
-    case IN_KEYS24: L(IN_KEYS24); break;
-    case IN_KEYS_W: L(IN_KEYS_W); break;
-    case IN_KEYS_B: L(IN_KEYS_B); break;
+  switch (kind) {  // keys only
+    KEY_KIND_CASES(L)
     default: L(IN_VAR); break;
   }
 #undef L
@@ -3212,20 +3222,29 @@ __global__ __launch_bounds__(ROUTE_NT) void k_route_count(const uint32_t* __rest
   if (threadIdx.x < world) cnt[(uint64_t)threadIdx.x * gridDim.x + blockIdx.x] = s_h[threadIdx.x];
 }
 
-// exclusive scan of cnt[world * nblk] (destination-major) into off; totals[d] = probes to d
-__global__ __launch_bounds__(1024) void k_route_scan(const uint32_t* __restrict__ cnt, uint32_t m,
-                                                     uint32_t nblk, uint32_t world, uint32_t* __restrict__ off,
-                                                     uint64_t* __restrict__ totals) {
-  __shared__ uint32_t s_tmp[1024 / WAVE + 1];
-  uint32_t carry = 0;
-  for (uint32_t base = 0; base < m; base += 1024) {
-    const uint32_t i = base + threadIdx.x;
+// exclusive scan of cnt[0, m) into off by one workgroup of 1,024 threads, in chunks of 1,024
+// (a chunk's total fits 32 bits); returns the total (s_tmp: 1024 / WAVE + 1 words)
+template <typename Carry, typename Count>
+__device__ __forceinline__ Carry chunked_excl_scan(const uint32_t* __restrict__ cnt, Count m,
+                                                   Carry* __restrict__ off, uint32_t* s_tmp) {
+  Carry carry = 0;
+  for (Count base = 0; base < m; base += 1024) {
+    const Count i = base + threadIdx.x;
     const uint32_t x = i < m ? cnt[i] : 0u;
     uint32_t tot;
     const uint32_t r = block_excl_scan<1024>(x, s_tmp, &tot);
     if (i < m) off[i] = carry + r;
     carry += tot;
   }
+  return carry;
+}
+
+// exclusive scan of cnt[world * nblk] (destination-major) into off; totals[d] = probes to d
+__global__ __launch_bounds__(1024) void k_route_scan(const uint32_t* __restrict__ cnt, uint32_t m,
+                                                     uint32_t nblk, uint32_t world, uint32_t* __restrict__ off,
+                                                     uint64_t* __restrict__ totals) {
+  __shared__ uint32_t s_tmp[1024 / WAVE + 1];
+  const uint32_t carry = chunked_excl_scan<uint32_t, uint32_t>(cnt, m, off, s_tmp);
   __syncthreads();
   if (threadIdx.x < world) {
     const uint32_t d = threadIdx.x;
@@ -3596,13 +3615,14 @@ __device__ __forceinline__ uint64_t field_ones64(uint32_t rvs) {
 // in E (line bytes [0, 16)); win(wi, w0, w1, w2) fetches dwords wi, wi + 1, wi + 2 of the
 // remainder area (line dwords 4 + wi ..; past the line: 0). Returns false when the image must
 // be walked instead (overflowed line, or a bucket too large for the 96-bit remainder window).
-template <typename Win>
-__device__ __forceinline__ bool line_decode_w(const v4u& E, Win win, uint32_t j, uint32_t remainder, uint32_t vs,
-                                              uint32_t rvs, uint64_t& found) {
+// routing_get_bucket_bounds (src/routing_filter.c:230-279) on the encoding dwords E of a probe
+// line: p1 = first bit after terminator j - 1 (0 for bucket 0), so p1 - j entries come before
+// bucket j; c = entries of bucket j = zeros from p1 up to terminator j. False when the image
+// must be walked: the overflow marker, or no terminator j in the 128 bits.
+__device__ __forceinline__ bool line_bounds(const v4u& E, uint32_t j, uint32_t& p1, uint32_t& c) {
   const uint32_t d0 = E.x, d1 = E.y, d2 = E.z, d3 = E.w;
   if ((d0 & d1 & d2 & d3) == 0xffffffffu) return false;  // overflow marker
-  // p1 = first bit after terminator j-1 (0 for bucket 0); entries before bucket j = p1 - j
-  uint32_t p1 = 0;
+  p1 = 0;
   if (j) {
     const uint32_t r = j - 1, c0 = __popc(d0), c1 = c0 + __popc(d1), c2 = c1 + __popc(d2);
     const uint32_t x = r >= c2 ? d3 : (r >= c1 ? d2 : (r >= c0 ? d1 : d0));
@@ -3610,14 +3630,36 @@ __device__ __forceinline__ bool line_decode_w(const v4u& E, Win win, uint32_t j,
     const uint32_t rr = r - (r >= c2 ? c2 : (r >= c1 ? c1 : (r >= c0 ? c0 : 0u)));
     p1 = base + select32(x, rr) + 1;
   }
-  const uint32_t s = p1 - j;
-  // c = entries of bucket j = zeros from p1 up to terminator j
   // (p1 <= 128: the encoding has j + 1 <= G terminators in 128 bits)
   const uint64_t e0 = (uint64_t)d1 << 32 | d0, e1 = (uint64_t)d3 << 32 | d2;
   const uint64_t y = p1 >= 128 ? 0ull
                      : (p1 >= 64 ? e1 >> (p1 - 64) : (e0 >> p1) | (p1 ? e1 << (64 - p1) : 0ull));
   if (y == 0) return false;
-  const uint32_t c = (uint32_t)__builtin_ctzll(y);
+  c = (uint32_t)__builtin_ctzll(y);
+  return true;
+}
+
+// found bits of a SWAR compare: Z = the top bits of the matching rvs-bit fields of W, each
+// field's low vs bits its value (vs == 0: bit 0 when anything matched)
+__device__ __forceinline__ uint64_t emit_matches(uint64_t Z, uint64_t W, uint32_t rvs, uint32_t vs) {
+  if (vs == 0) return Z ? 1ull : 0ull;
+  const uint32_t vmask = (1u << vs) - 1;
+  uint64_t found = 0;
+  while (Z) {  // one pass per match (usually 0 or 1)
+    const uint32_t p = (uint32_t)__builtin_ctzll(Z) + 1 - rvs;  // the field's first bit
+    const uint32_t val = (uint32_t)(W >> p) & vmask;
+    if (val < 64) found |= 1ull << val;
+    Z &= Z - 1;
+  }
+  return found;
+}
+
+template <typename Win>
+__device__ __forceinline__ bool line_decode_w(const v4u& E, Win win, uint32_t j, uint32_t remainder, uint32_t vs,
+                                              uint32_t rvs, uint64_t& found) {
+  uint32_t p1, c;
+  if (!line_bounds(E, j, p1, c)) return false;
+  const uint32_t s = p1 - j;
   found = 0;
   if (c == 0 || rvs == 0) {
     if (c && remainder == 0) found = 1;  // rvs == 0: every entry matches, value 0
@@ -3643,17 +3685,8 @@ __device__ __forceinline__ bool line_decode_w(const v4u& E, Win win, uint32_t j,
     const uint64_t H = (L << (rvs - 1)) & valid;          // top bit of each remainder part
     const uint64_t MH = M & ~H;
     const uint64_t Y = (W ^ ((uint64_t)(remainder << vs) * L)) & M;
-    uint64_t Z = H & ~((((Y & MH) + MH) | Y) & H);  // top bits of the matching fields
-    if (vs == 0) {
-      found = Z ? 1ull : 0ull;
-    } else {
-      while (Z) {  // one pass per match (usually 0 or 1)
-        const uint32_t p = (uint32_t)__builtin_ctzll(Z) + 1 - rvs;  // the field's first bit
-        const uint32_t val = (uint32_t)(W >> p) & vmask;
-        if (val < 64) found |= 1ull << val;
-        Z &= Z - 1;
-      }
-    }
+    const uint64_t Z = H & ~((((Y & MH) + MH) | Y) & H);  // top bits of the matching fields
+    found = emit_matches(Z, W, rvs, vs);
     return true;
   }
   const uint32_t rvmask = rvs >= 32 ? 0xffffffffu : ((1u << rvs) - 1);
@@ -3693,10 +3726,6 @@ __device__ __forceinline__ bool line_decode(const v4u (&Q)[4], uint32_t j, uint3
 // keys (their per-wave 4 KiB LDS windows; C5 0.325 vs 0.337 ms)
 #ifndef RF_PROBE_NT
 #define RF_PROBE_NT 1024
-#endif
-// quad-cooperative probe-line gather (k_probe); 0 = one lane loads its own line
-#ifndef RF_PROBE_QUAD
-#define RF_PROBE_QUAD 1
 #endif
 constexpr int PROBE_NT = RF_PROBE_NT;
 constexpr int PROBE_NT_VAR = 256;
@@ -3755,6 +3784,15 @@ __device__ __forceinline__ uint4 load_pplan(const uint4* __restrict__ pplans, ui
   return fid < nf ? pplans[fid] : make_uint4(0, 0, 0, 1);
 }
 
+// hash -> fingerprint -> bucket (index << lis | bucket in index) and remainder of a filter
+// that keeps rem remainder bits (src/routing_filter.c:1004-1012)
+__device__ __forceinline__ void split_fp(uint32_t h, uint32_t fp_size, uint32_t rem, uint32_t& bucket,
+                                         uint32_t& remainder) {
+  const uint32_t fp = h >> (32 - fp_size);
+  bucket = rem >= 32 ? 0u : fp >> rem;
+  remainder = fp & (rem >= 32 ? 0xffffffffu : ((1u << rem) - 1));
+}
+
 // The line half of one probe once its hash and probe plan P are known: bucket, remainder,
 // the probe line and its decode. Returns false when the image must be walked instead
 // (overflowed line, a bucket too large for the window, or a filter without lines). When the
@@ -3767,9 +3805,8 @@ __device__ __forceinline__ bool probe_line(const uint4 P, uint32_t h, const uint
   r = 0;
   if (P.w) return true;  // unknown filter, or its build failed: nothing found
   if (!lgl) return false;
-  const uint32_t fp = h >> (32 - fp_size);
-  const uint32_t bucket = rem >= 32 ? 0u : fp >> rem;  // index << lis | bucket in index
-  const uint32_t remainder = fp & (rem >= 32 ? 0xffffffffu : ((1u << rem) - 1));
+  uint32_t bucket, remainder;
+  split_fp(h, fp_size, rem, bucket, remainder);
   const v4u* lp = reinterpret_cast<const v4u*>(lines + ((uint64_t)P.y + (bucket >> (lgl - 1))) * 4);
   v4u Q[4];
 #pragma unroll
@@ -3783,9 +3820,8 @@ __device__ __forceinline__ uint64_t probe_walk(const uint4 P, uint32_t h, uint32
                                                const uint8_t* __restrict__ pages, const uint64_t* __restrict__ slots,
                                                uint32_t fp_size, uint32_t lis, uint32_t page_size) {
   const uint32_t vs = P.x & 0xff, rem = (P.x >> 8) & 0xff, rvs = (P.x >> 16) & 0xff;
-  const uint32_t fp = h >> (32 - fp_size);
-  const uint32_t bucket = rem >= 32 ? 0u : fp >> rem;
-  const uint32_t remainder = fp & (rem >= 32 ? 0xffffffffu : ((1u << rem) - 1));
+  uint32_t bucket, remainder;
+  split_fp(h, fp_size, rem, bucket, remainder);
   const uint64_t hdr = slots[P.z + (bucket >> lis)];
   const uint8_t* pg = pages + (uint64_t)plans[fid].page_base * page_size;
   return probe_stream(bucket & ((1u << lis) - 1), remainder, vs, rvs, pg, hdr, lis);
@@ -3829,21 +3865,8 @@ __device__ __forceinline__ uint64_t sload64(const void* p) {
 // for the 96-bit window or for one 64-bit SWAR compare).
 __device__ __forceinline__ bool line_decode_u(const uint32_t* Lw, uint32_t j, uint32_t remainder, uint32_t vs,
                                               uint32_t rvs, uint64_t L, uint64_t& found) {
-  const v4u E = *reinterpret_cast<const v4u*>(Lw);
-  const uint32_t d0 = E.x, d1 = E.y, d2 = E.z, d3 = E.w;
-  if ((d0 & d1 & d2 & d3) == 0xffffffffu) return false;  // overflow marker
-  uint32_t p1 = 0;  // first bit after terminator j - 1
-  if (j) {
-    const uint32_t r = j - 1, c0 = __popc(d0), c1 = c0 + __popc(d1), c2 = c1 + __popc(d2);
-    const uint32_t x = r >= c2 ? d3 : (r >= c1 ? d2 : (r >= c0 ? d1 : d0));
-    const uint32_t base = r >= c2 ? 96u : (r >= c1 ? 64u : (r >= c0 ? 32u : 0u));
-    const uint32_t rr = r - (r >= c2 ? c2 : (r >= c1 ? c1 : (r >= c0 ? c0 : 0u)));
-    p1 = base + select32(x, rr) + 1;
-  }
-  const uint64_t e0 = (uint64_t)d1 << 32 | d0, e1 = (uint64_t)d3 << 32 | d2;
-  const uint64_t y = p1 >= 128 ? 0ull : (p1 >= 64 ? e1 >> (p1 - 64) : (e0 >> p1) | (p1 ? e1 << (64 - p1) : 0ull));
-  if (y == 0) return false;
-  const uint32_t c = (uint32_t)__builtin_ctzll(y);  // entries of bucket j
+  uint32_t p1, c;
+  if (!line_bounds(*reinterpret_cast<const v4u*>(Lw), j, p1, c)) return false;
   found = 0;
   if (c == 0) return true;
   const uint32_t b = (p1 - j) * rvs, nb = c * rvs, wi = b >> 5, off = b & 31;
@@ -3856,18 +3879,8 @@ __device__ __forceinline__ bool line_decode_u(const uint32_t* Lw, uint32_t j, ui
   const uint64_t W = (uint64_t)__builtin_amdgcn_alignbit(w2, w1, off) << 32 | __builtin_amdgcn_alignbit(w1, w0, off);
   const uint64_t Y = W ^ ((uint64_t)(remainder << vs) * L);
   const uint64_t valid = nb == 64 ? ~0ull : (1ull << nb) - 1;
-  uint64_t Z = H & valid & ~(((Y & MH) + MH) | Y);  // top bits of the matching fields
-  if (vs == 0) {
-    found = Z ? 1ull : 0ull;
-  } else {
-    const uint32_t vmask = (1u << vs) - 1;
-    while (Z) {  // one pass per match (usually 0 or 1)
-      const uint32_t p = (uint32_t)__builtin_ctzll(Z) + 1 - rvs;  // the field's first bit
-      const uint32_t val = (uint32_t)(W >> p) & vmask;
-      if (val < 64) found |= 1ull << val;
-      Z &= Z - 1;
-    }
-  }
+  const uint64_t Z = H & valid & ~(((Y & MH) + MH) | Y);  // top bits of the matching fields
+  found = emit_matches(Z, W, rvs, vs);
   return true;
 }
 
@@ -3881,6 +3894,62 @@ __device__ __forceinline__ bool line_decode_u(const uint32_t* Lw, uint32_t j, ui
 #endif
 constexpr uint32_t FAST_KSTRIDE = RF_FAST_KSTRIDE;
 constexpr int FAST_WBUF = (3 * FAST_KSTRIDE + 1024) / 16 + 1;
+
+// ---- a wave's 64 24-byte keys (1,536 contiguous bytes at kb, 16-byte aligned) through LDS ----
+// Read with 16-byte coalesced loads -- 12 cache lines per wave, where three strided 8-byte
+// loads per lane touch 36 -- into sw[0..96) and handed to their lanes from there.
+// Full wave: LDS-DMA, no VGPR round trip. Issue only: the caller waits (vmcnt) and syncs the
+// wave (wave_sync_lds) before keys24_hash_lds, and may put other loads in between.
+__device__ __forceinline__ void keys24_issue_dma(const uint8_t* kb, v4u* sw, uint32_t lane) {
+  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(kb + lane * 16),
+                                   (__attribute__((address_space(3))) void*)sw, 16, 0, 2);
+  if (lane < 32)
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(kb + 1024 + lane * 16),
+                                     (__attribute__((address_space(3))) void*)(sw + WAVE), 16, 0, 2);
+}
+// Partial wave (bytes < 1,536, a multiple of 24): plain loads; the caller syncs the wave
+__device__ __forceinline__ void keys24_stage_partial(const uint8_t* kb, uint32_t bytes, v4u* sw, uint32_t lane) {
+  const v4u* src = reinterpret_cast<const v4u*>(kb);
+#pragma unroll
+  for (uint32_t j = lane; j < 96; j += WAVE) {
+    if ((j + 1) * 16 <= bytes) {
+      sw[j] = __builtin_nontemporal_load(src + j);
+    } else if (j * 16 < bytes) {  // an odd key count ends on an 8-byte half
+      const uint64_t t = __builtin_nontemporal_load(reinterpret_cast<const uint64_t*>(src + j));
+      sw[j] = v4u{(uint32_t)t, (uint32_t)(t >> 32), 0u, 0u};
+    }
+  }
+}
+// XXH32 of the lane's key in sw
+__device__ __forceinline__ uint32_t keys24_hash_lds(const v4u* sw, uint32_t lane, uint32_t seed) {
+  const uint2* k2 = reinterpret_cast<const uint2*>(sw) + 3 * lane;
+  const uint2 a = k2[0], b = k2[1], c = k2[2];
+  const uint32_t w[6] = {a.x, a.y, b.x, b.y, c.x, c.y};
+  return xxh32_24(w, seed);
+}
+
+// Quad-cooperative line gather by LDS-DMA: instruction K fetches the 64-B lines of probes
+// 4g + K of all 16 quads g -- `lo`, the line's byte offset from fb, comes from lane 4g + K by a
+// DPP quad broadcast -- 16 B per lane, to sb + K * STRIDE (lane L -> byte 16 L there). Lane q of
+// a quad (q = lane & 3) loads quarter q, or with ROT quarter (q + K) & 3. The callers explain
+// their layouts.
+template <int K, uint32_t STRIDE, bool ROT>
+__device__ __forceinline__ void quad_gather_k(const uint8_t* fb, uint32_t lo, uint32_t q, uint32_t q16, uint8_t* sb) {
+  const uint32_t lk = (uint32_t)__builtin_amdgcn_mov_dpp((int)lo, K * 0x55, 0xf, 0xf, false);
+  const uint8_t* src;
+  if constexpr (ROT) src = fb + lk + (((q + K) & 3u) << 4);
+  else src = fb + (lk + q16);
+  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+                                   (__attribute__((address_space(3))) void*)(sb + K * STRIDE), 16, 0, 0);
+}
+template <uint32_t STRIDE, bool ROT>
+__device__ __forceinline__ void quad_gather(const uint8_t* fb, uint32_t lo, uint32_t q, uint8_t* sb) {
+  const uint32_t q16 = q << 4;  // the unrotated quarter's bytes, ahead of the broadcasts
+  quad_gather_k<0, STRIDE, ROT>(fb, lo, q, q16, sb);
+  quad_gather_k<1, STRIDE, ROT>(fb, lo, q, q16, sb);
+  quad_gather_k<2, STRIDE, ROT>(fb, lo, q, q16, sb);
+  quad_gather_k<3, STRIDE, ROT>(fb, lo, q, q16, sb);
+}
 
 // Sweep 0.. of a full wave of one filter: hash (24-byte keys staged through LDS by LDS-DMA, or
 // hashes), gather each probe's 64-B line (quad-cooperative LDS-DMA), decode, one coalesced
@@ -3901,14 +3970,7 @@ __device__ __forceinline__ bool probe_fast(const uint4* __restrict__ pplans, con
   // stages them itself (the same LDS slots, the same bytes).
   uint32_t h = 0;
   if constexpr (KIND == IN_KEYS24) {
-    // the wave's 64 keys (1,536 contiguous bytes): 16-byte LDS-DMA loads, 12 cache lines
-    const uint8_t* kb = static_cast<const uint8_t*>(in0) + wf * 24;
-    const uint8_t* kb2 = kb + 1024;
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(kb + lane * 16),
-                                     (__attribute__((address_space(3))) void*)sw, 16, 0, 2);
-    if (lane < 32)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(kb2 + lane * 16),
-                                       (__attribute__((address_space(3))) void*)(sw + WAVE), 16, 0, 2);
+    keys24_issue_dma(static_cast<const uint8_t*>(in0) + wf * 24, sw, lane);
   } else {
     h = __builtin_nontemporal_load(static_cast<const uint32_t*>(in0) + wf + lane);
   }
@@ -3923,26 +3985,16 @@ __device__ __forceinline__ bool probe_fast(const uint4* __restrict__ pplans, con
   if constexpr (KIND == IN_KEYS24) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     wave_sync_lds();
-    const uint2* k2 = reinterpret_cast<const uint2*>(sw) + 3 * lane;
-    const uint2 a = k2[0], b = k2[1], c = k2[2];
-    const uint32_t w[6] = {a.x, a.y, b.x, b.y, c.x, c.y};
-    h = xxh32_24(w, seed);
+    h = keys24_hash_lds(sw, lane, seed);
   }
   const uint32_t lgG = lgl - 1;
+  // rem is in [1, 32) here: split_fp without its guards
   const uint32_t fp = h >> (32 - fp_size);
   const uint32_t bucket = fp >> rem;
   const uint32_t remainder = fp & ((1u << rem) - 1);
   const uint8_t* fb = reinterpret_cast<const uint8_t*>(lines) + ((uint64_t)U.y << 6);  // the filter's lines
-  const uint32_t lo = (bucket >> lgG) << 6, q16 = (lane & 3) << 4;
   uint8_t* sb = reinterpret_cast<uint8_t*>(sw);
-#define RF_FAST_LOAD(k)                                                                                       \
-  {                                                                                                           \
-    const uint32_t lk = (uint32_t)__builtin_amdgcn_mov_dpp((int)lo, (k) * 0x55, 0xf, 0xf, false);             \
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(fb + (lk + q16)),        \
-                                     (__attribute__((address_space(3))) void*)(sb + (k) * FAST_KSTRIDE), 16, 0, 0); \
-  }
-  RF_FAST_LOAD(0) RF_FAST_LOAD(1) RF_FAST_LOAD(2) RF_FAST_LOAD(3)
-#undef RF_FAST_LOAD
+  quad_gather<FAST_KSTRIDE, false>(fb, (bucket >> lgG) << 6, lane & 3, sb);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   wave_sync_lds();
   const uint32_t* Lw = reinterpret_cast<const uint32_t*>(sb + (lane & 3) * FAST_KSTRIDE + (lane >> 2) * 64);
@@ -3950,14 +4002,6 @@ __device__ __forceinline__ bool probe_fast(const uint4* __restrict__ pplans, con
   uint64_t r;
   if (!line_decode_u(Lw, bucket & ((1u << lgG) - 1), remainder, vs, rvs, L, r))
     r = probe_walk(U, h, fs, plans, pages, slots, fp_size, lis, page_size);
-#ifdef RF_PROBE_PAD
-  {  // diagnostics builds only (tools/ab_build.sh): RF_PROBE_PAD extra VALU per lane
-    uint32_t x = h;
-#pragma unroll
-    for (int k = 0; k < RF_PROBE_PAD; k++) asm volatile("v_add_u32 %0, %0, %1" : "+v"(x) : "v"(remainder));
-    asm volatile("" ::"v"(x));
-  }
-#endif
   __builtin_nontemporal_store(r, found + wf + lane);
   return true;
 }
@@ -3984,14 +4028,13 @@ __global__ __launch_bounds__(probe_nt(KIND)) void k_probe(const uint4* __restric
   constexpr bool WAVE_VAR = KIND == IN_VAR;
   // per wave: the 24-byte keys' staging (96 x 16 B), then the quad-gathered probe lines
   // (64 x 64 B); variable-length keys stage their window in s_vk and reuse it for the lines
-  constexpr bool QUAD = RF_PROBE_QUAD;
-  constexpr int WBUF = (QUAD && !WAVE_VAR) ? FAST_WBUF : (WAVE_KEYS ? 96 : 1);
+  constexpr int WBUF = WAVE_VAR ? 1 : FAST_WBUF;
   __shared__ v4u s_wbuf[NT / WAVE][WBUF];
   constexpr uint32_t VCAP = 4096;
   __shared__ __attribute__((aligned(16))) uint32_t s_vk[WAVE_VAR ? NT / WAVE : 1][WAVE_VAR ? VCAP / 4 + 4 : 1];
   const uint32_t lane = threadIdx.x & (WAVE - 1);
   const uint64_t wf = i0 - lane;  // the wave's first probe
-  if constexpr ((KIND == IN_KEYS24 || KIND == IN_HASH) && QUAD) {
+  if constexpr (KIND == IN_KEYS24 || KIND == IN_HASH) {
     if (runs) {
       const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x) / WAVE;
       const uint64_t wfs = (uint64_t)xcd_chunk(blockIdx.x, gridDim.x) * NT + wv * WAVE;  // = wf, in SGPRs
@@ -4001,44 +4044,22 @@ __global__ __launch_bounds__(probe_nt(KIND)) void k_probe(const uint4* __restric
     }
   }
   if constexpr (WAVE_KEYS) {
-    // 24-byte keys: the wave's 64 keys (1,536 contiguous bytes) are read with 16-byte
-    // coalesced loads -- 12 cache lines per wave, where three strided 8-byte loads per lane
-    // touch 36 -- and handed to their lanes through LDS
+    // 24-byte keys: staged through LDS (keys24_*)
     if (wf < n) {  // uniform per wave
       if (i0 < n) fid = runs ? tab_filter(wave_tab, runs, num_filters, i0) : __builtin_nontemporal_load(filter_id + i0);
       pp = load_pplan(pplans, fid, num_filters);  // in flight with the key loads
       if (((uintptr_t)in0 & 15) == 0) {
         v4u* sw = s_wbuf[threadIdx.x / WAVE];
         const uint32_t bytes = (uint32_t)min<uint64_t>(WAVE, n - wf) * 24;
-        const v4u* src = reinterpret_cast<const v4u*>(static_cast<const uint8_t*>(in0) + wf * 24);
-        if (bytes == WAVE * 24) {  // full wave: LDS-DMA, no VGPR round trip
-#pragma unroll
-          for (uint32_t it = 0; it < 2; it++) {
-            const uint32_t j = lane + it * WAVE;
-            if (j < 96)
-              __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + j),
-                                               (__attribute__((address_space(3))) void*)(sw + it * WAVE), 16, 0, 2);
-          }
+        const uint8_t* kb = static_cast<const uint8_t*>(in0) + wf * 24;
+        if (bytes == WAVE * 24) {
+          keys24_issue_dma(kb, sw, lane);
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        } else
-#pragma unroll
-        for (uint32_t j = lane; j < 96; j += WAVE) {
-          if ((j + 1) * 16 <= bytes) {
-            sw[j] = __builtin_nontemporal_load(src + j);
-          } else if (j * 16 < bytes) {  // an odd key count ends on an 8-byte half
-            const uint64_t t = __builtin_nontemporal_load(reinterpret_cast<const uint64_t*>(src + j));
-            sw[j] = v4u{(uint32_t)t, (uint32_t)(t >> 32), 0u, 0u};
-          }
+        } else {
+          keys24_stage_partial(kb, bytes, sw, lane);
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        if (i0 < n) {
-          const uint2* k2 = reinterpret_cast<const uint2*>(sw) + 3 * lane;
-          const uint2 a = k2[0], b = k2[1], c = k2[2];
-          uint32_t w[6] = {a.x, a.y, b.x, b.y, c.x, c.y};
-          h = xxh32_24(w, seed);
-        }
+        wave_sync_lds();
+        if (i0 < n) h = keys24_hash_lds(sw, lane, seed);
       } else if (i0 < n) {
         h = hash_key<KIND, true>(in0, offs, key_len, seed, i0);
       }
@@ -4072,66 +4093,53 @@ __global__ __launch_bounds__(probe_nt(KIND)) void k_probe(const uint4* __restric
   }
   const uint32_t fs = __builtin_amdgcn_readfirstlane(fid);
   const bool uniform = __builtin_amdgcn_ballot_w64(fid != fs) == 0;
-  if constexpr (QUAD) {
-    // Quad-cooperative line gather (full waves probing one filter -- the usual case with
-    // per-filter runs; the conditions are wave-uniform, so every lane takes part in the
-    // lane exchanges). One 64-B line per probe, but each wave instruction fetches 16 whole
-    // lines (quad g = lanes 4g..4g+3 reads one line, 16 B per lane) instead of a 16-B piece
-    // of 64 different lines: 64 line requests per wave instead of 256. Instruction k gathers
-    // the lines of probes 4g + k (their line index comes from lane 4g + k by a DPP quad
-    // broadcast) straight into LDS (LDS-DMA, lane L -> byte 16 L of the k-th KiB); lane q of
-    // the quad loads quarter (q + k) & 3, so probe p finds quarter j of its line at
-    // KiB p & 3, line slot p >> 2, 16-B slot (j - p) & 3 -- the 16 lanes of each ds_read_b128
-    // lane group then hit 16 distinct 4-bank groups (no conflicts). C2 probe 0.842 -> 0.821
-    // ms, C3 2.577 -> 2.537 ms per 256M (profiles/r04_quad_ab.json).
-    if (wf + WAVE <= n && uniform) {
-      const uint4 U = make_uint4(__builtin_amdgcn_readfirstlane(pp.x), __builtin_amdgcn_readfirstlane(pp.y),
-                                 __builtin_amdgcn_readfirstlane(pp.z), __builtin_amdgcn_readfirstlane(pp.w));
-      const uint32_t vs = U.x & 0xff, rem = (U.x >> 8) & 0xff, rvs = (U.x >> 16) & 0xff, lgl = U.x >> 24;
-      if (!U.w && lgl) {
-        const uint32_t q = lane & 3;
-        const uint32_t fp = h >> (32 - fp_size);
-        const uint32_t bucket = rem >= 32 ? 0u : fp >> rem;
-        const uint32_t remainder = fp & (rem >= 32 ? 0xffffffffu : ((1u << rem) - 1));
-        // the filter's line table (uniform) and this probe's line within it as a 32-bit byte
-        // offset: each load is a scalar base plus one VGPR offset (no per-load 64-bit math)
-        const uint8_t* fb = reinterpret_cast<const uint8_t*>(lines) + ((uint64_t)U.y << 6);
-        const uint32_t lo = (bucket >> (lgl - 1)) << 6;
-        v4u* sw;
-        if constexpr (WAVE_VAR) sw = reinterpret_cast<v4u*>(s_vk[threadIdx.x / WAVE]);
-        else sw = s_wbuf[threadIdx.x / WAVE];
-#define RF_QUAD_LOAD(k)                                                                                      \
-  {                                                                                                          \
-    const uint32_t lk = (uint32_t)__builtin_amdgcn_mov_dpp((int)lo, (k) * 0x55, 0xf, 0xf, false);            \
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(fb + lk + (((q + (k)) & 3u) << 4)), \
-                                     (__attribute__((address_space(3))) void*)(sw + (k) * WAVE), 16, 0, 0);  \
-  }
-        RF_QUAD_LOAD(0) RF_QUAD_LOAD(1) RF_QUAD_LOAD(2) RF_QUAD_LOAD(3)
-#undef RF_QUAD_LOAD
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        // this probe's line in LDS: quarter j at L32 + ((j - lane) & 3) * 4 (dwords). The
-        // decode reads the encoding quarter into registers and only the three dwords of its
-        // bucket's remainder window from LDS (instead of all four quarters and a 21-way select:
-        // the probe is VALU-bound as much as memory-bound)
-        const uint32_t* L32 = reinterpret_cast<const uint32_t*>(sw + (lane & 3) * WAVE + (lane >> 2) * 4);
-        const v4u E = *reinterpret_cast<const v4u*>(L32 + ((0u - lane) & 3u) * 4);
-        auto win = [&](uint32_t wi, uint32_t& w0, uint32_t& w1, uint32_t& w2) {
-          // line dword d = 4 + wi + t (d & 15: dwords past the line are never used, the
-          // window's bits beyond the bucket are masked)
-          auto dw = [&](uint32_t d) -> uint32_t { d &= 15u; return L32[(((d >> 2) - lane) & 3u) * 4 + (d & 3u)]; };
-          w0 = dw(4 + wi);
-          w1 = dw(5 + wi);
-          w2 = dw(6 + wi);
-        };
-        uint64_t r;
-        if (!line_decode_w(E, win, bucket & ((1u << (lgl - 1)) - 1), remainder, vs, rvs, r))
-          r = probe_walk(U, h, fs, plans, pages, slots, fp_size, lis, page_size);
-        __builtin_nontemporal_store(r, found + i0);
-        return;
-      }
+  // Quad-cooperative line gather (full waves probing one filter -- the usual case with
+  // per-filter runs; the conditions are wave-uniform, so every lane takes part in the
+  // lane exchanges). One 64-B line per probe, but each wave instruction fetches 16 whole
+  // lines (quad g = lanes 4g..4g+3 reads one line, 16 B per lane) instead of a 16-B piece
+  // of 64 different lines: 64 line requests per wave instead of 256. Instruction k gathers
+  // the lines of probes 4g + k (their line index comes from lane 4g + k by a DPP quad
+  // broadcast) straight into LDS (LDS-DMA, lane L -> byte 16 L of the k-th KiB); lane q of
+  // the quad loads quarter (q + k) & 3, so probe p finds quarter j of its line at
+  // KiB p & 3, line slot p >> 2, 16-B slot (j - p) & 3 -- the 16 lanes of each ds_read_b128
+  // lane group then hit 16 distinct 4-bank groups (no conflicts). C2 probe 0.842 -> 0.821
+  // ms, C3 2.577 -> 2.537 ms per 256M (profiles/r04_quad_ab.json).
+  if (wf + WAVE <= n && uniform) {
+    const uint4 U = make_uint4(__builtin_amdgcn_readfirstlane(pp.x), __builtin_amdgcn_readfirstlane(pp.y),
+                               __builtin_amdgcn_readfirstlane(pp.z), __builtin_amdgcn_readfirstlane(pp.w));
+    const uint32_t vs = U.x & 0xff, rem = (U.x >> 8) & 0xff, rvs = (U.x >> 16) & 0xff, lgl = U.x >> 24;
+    if (!U.w && lgl) {
+      uint32_t bucket, remainder;
+      split_fp(h, fp_size, rem, bucket, remainder);
+      // the filter's line table (uniform) and this probe's line within it as a 32-bit byte
+      // offset: each load is a scalar base plus one VGPR offset (no per-load 64-bit math)
+      const uint8_t* fb = reinterpret_cast<const uint8_t*>(lines) + ((uint64_t)U.y << 6);
+      const uint32_t lo = (bucket >> (lgl - 1)) << 6;
+      v4u* sw;
+      if constexpr (WAVE_VAR) sw = reinterpret_cast<v4u*>(s_vk[threadIdx.x / WAVE]);
+      else sw = s_wbuf[threadIdx.x / WAVE];
+      quad_gather<WAVE * 16, true>(fb, lo, lane & 3, reinterpret_cast<uint8_t*>(sw));
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      wave_sync_lds();
+      // this probe's line in LDS: quarter j at L32 + ((j - lane) & 3) * 4 (dwords). The
+      // decode reads the encoding quarter into registers and only the three dwords of its
+      // bucket's remainder window from LDS (instead of all four quarters and a 21-way select:
+      // the probe is VALU-bound as much as memory-bound)
+      const uint32_t* L32 = reinterpret_cast<const uint32_t*>(sw + (lane & 3) * WAVE + (lane >> 2) * 4);
+      const v4u E = *reinterpret_cast<const v4u*>(L32 + ((0u - lane) & 3u) * 4);
+      auto win = [&](uint32_t wi, uint32_t& w0, uint32_t& w1, uint32_t& w2) {
+        // line dword d = 4 + wi + t (d & 15: dwords past the line are never used, the
+        // window's bits beyond the bucket are masked)
+        auto dw = [&](uint32_t d) -> uint32_t { d &= 15u; return L32[(((d >> 2) - lane) & 3u) * 4 + (d & 3u)]; };
+        w0 = dw(4 + wi);
+        w1 = dw(5 + wi);
+        w2 = dw(6 + wi);
+      };
+      uint64_t r;
+      if (!line_decode_w(E, win, bucket & ((1u << (lgl - 1)) - 1), remainder, vs, rvs, r))
+        r = probe_walk(U, h, fs, plans, pages, slots, fp_size, lis, page_size);
+      __builtin_nontemporal_store(r, found + i0);
+      return;
     }
   }
   // one lane per probe: partial waves, waves across filters, filters without lines
@@ -4172,14 +4180,7 @@ __global__ __launch_bounds__(probe_nt(KIND)) void k_probe_floor(const uint4* __r
   uint32_t h = 0;
   const bool full = wf + WAVE <= n;
   if constexpr (KIND == IN_KEYS24) {  // requested before the filter is known, as the fast path
-    const uint8_t* kb = static_cast<const uint8_t*>(in0) + wf * 24;
-    if (full) {
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(kb + lane * 16),
-                                       (__attribute__((address_space(3))) void*)sw, 16, 0, 2);
-      if (lane < 32)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(kb + 1024 + lane * 16),
-                                         (__attribute__((address_space(3))) void*)(sw + WAVE), 16, 0, 2);
-    }
+    if (full) keys24_issue_dma(static_cast<const uint8_t*>(in0) + wf * 24, sw, lane);
   } else {
     if (full) h = __builtin_nontemporal_load(static_cast<const uint32_t*>(in0) + wf + lane);
   }
@@ -4208,16 +4209,8 @@ __global__ __launch_bounds__(probe_nt(KIND)) void k_probe_floor(const uint4* __r
   }
   const uint32_t bucket = (h >> (32 - fp_size)) >> rem;
   const uint8_t* fb = reinterpret_cast<const uint8_t*>(lines) + ((uint64_t)base << 6);
-  const uint32_t lo = (bucket >> (lgl - 1)) << 6, q16 = (lane & 3) << 4;
   uint8_t* sb = reinterpret_cast<uint8_t*>(sw);
-#define RF_FLOOR_LOAD(k)                                                                                      \
-  {                                                                                                           \
-    const uint32_t lk = (uint32_t)__builtin_amdgcn_mov_dpp((int)lo, (k) * 0x55, 0xf, 0xf, false);             \
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(fb + (lk + q16)),        \
-                                     (__attribute__((address_space(3))) void*)(sb + (k) * FAST_KSTRIDE), 16, 0, 0); \
-  }
-  RF_FLOOR_LOAD(0) RF_FLOOR_LOAD(1) RF_FLOOR_LOAD(2) RF_FLOOR_LOAD(3)
-#undef RF_FLOOR_LOAD
+  quad_gather<FAST_KSTRIDE, false>(fb, (bucket >> (lgl - 1)) << 6, lane & 3, sb);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   wave_sync_lds();
   const v4u E = *reinterpret_cast<const v4u*>(sb + (lane & 3) * FAST_KSTRIDE + (lane >> 2) * 64);
@@ -4232,9 +4225,8 @@ __device__ __forceinline__ uint64_t probe_group(const ProbeGroup& G, uint32_t h)
   uint64_t r = 0;
   if (!probe_line(P, h, G.lines, fp_size, r)) {  // overflowed line / no lines: walk the image
     const uint32_t vs = G.x & 0xff, rem = (G.x >> 8) & 0xff, rvs = (G.x >> 16) & 0xff;
-    const uint32_t fp = h >> (32 - fp_size);
-    const uint32_t bucket = rem >= 32 ? 0u : fp >> rem;
-    const uint32_t remainder = fp & (rem >= 32 ? 0xffffffffu : ((1u << rem) - 1));
+    uint32_t bucket, remainder;
+    split_fp(h, fp_size, rem, bucket, remainder);
     r = probe_stream(bucket & ((1u << lis) - 1), remainder, vs, rvs, G.pages, G.slots[bucket >> lis], lis);
   }
   return r;
@@ -4348,33 +4340,15 @@ __global__ __launch_bounds__(FAN_NT) void k_probe_fanout(const void* __restrict_
     if constexpr (WAVE_KEYS) {
       if (((uintptr_t)in0 & 15) == 0) {
         v4u* sw = s_keys[wv];
-        const v4u* src = reinterpret_cast<const v4u*>(static_cast<const uint8_t*>(in0) + wf * 24);
-        if (nk == WAVE) {  // 1,536 contiguous bytes by LDS-DMA (probe_fast)
-          __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + lane),
-                                           (__attribute__((address_space(3))) void*)sw, 16, 0, 2);
-          if (lane < 32)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + WAVE + lane),
-                                             (__attribute__((address_space(3))) void*)(sw + WAVE), 16, 0, 2);
+        const uint8_t* kb = static_cast<const uint8_t*>(in0) + wf * 24;
+        if (nk == WAVE) {
+          keys24_issue_dma(kb, sw, lane);
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         } else {
-          const uint32_t bytes = nk * 24;
-#pragma unroll
-          for (uint32_t j = lane; j < 96; j += WAVE) {
-            if ((j + 1) * 16 <= bytes) {
-              sw[j] = __builtin_nontemporal_load(src + j);
-            } else if (j * 16 < bytes) {  // an odd key count ends on an 8-byte half
-              const uint64_t t = __builtin_nontemporal_load(reinterpret_cast<const uint64_t*>(src + j));
-              sw[j] = v4u{(uint32_t)t, (uint32_t)(t >> 32), 0u, 0u};
-            }
-          }
+          keys24_stage_partial(kb, nk * 24, sw, lane);
         }
         wave_sync_lds();
-        if (lane < nk) {
-          const uint2* k2 = reinterpret_cast<const uint2*>(sw) + 3 * lane;
-          const uint2 a = k2[0], b = k2[1], c = k2[2];
-          const uint32_t w[6] = {a.x, a.y, b.x, b.y, c.x, c.y};
-          h = xxh32_24(w, seed);
-        }
+        if (lane < nk) h = keys24_hash_lds(sw, lane, seed);
       } else if (lane < nk) {
         h = hash_key<KIND, true>(in0, nullptr, key_len, seed, wf + lane);
       }
@@ -4445,9 +4419,9 @@ __global__ __launch_bounds__(FAN_NT) void k_probe_fanout(const void* __restrict_
         pj[u] = pr[u] = 0;
         if (st[u] == 1) {
           const uint32_t rem = (px[u] >> 8) & 0xff, lgl = px[u] >> 24, fp_size = pf[u] & 0xff;
-          const uint32_t fp = hh[u] >> (32 - fp_size);
-          const uint32_t bucket = rem >= 32 ? 0u : fp >> rem;
-          pr[u] = fp & (rem >= 32 ? 0xffffffffu : ((1u << rem) - 1));
+          uint32_t bucket, remainder;
+          split_fp(hh[u], fp_size, rem, bucket, remainder);
+          pr[u] = remainder;
           pj[u] = bucket & ((1u << (lgl - 1)) - 1);
           const v4u* lp = reinterpret_cast<const v4u*>((uintptr_t)pl[u]) + (uint64_t)(bucket >> (lgl - 1)) * 4;
 #pragma unroll
@@ -4509,15 +4483,7 @@ __global__ __launch_bounds__(FC_NT) void k_found_count(const uint64_t* __restric
 __global__ __launch_bounds__(1024) void k_found_scan(const uint32_t* __restrict__ cnt, uint64_t ntiles,
                                                      uint64_t* __restrict__ off, uint64_t* __restrict__ count) {
   __shared__ uint32_t s_tmp[1024 / WAVE + 1];
-  uint64_t carry = 0;
-  for (uint64_t base = 0; base < ntiles; base += 1024) {
-    const uint64_t i = base + threadIdx.x;
-    const uint32_t x = i < ntiles ? cnt[i] : 0u;
-    uint32_t tot;
-    const uint32_t r = block_excl_scan<1024>(x, s_tmp, &tot);
-    if (i < ntiles) off[i] = carry + r;
-    carry += tot;
-  }
+  const uint64_t carry = chunked_excl_scan<uint64_t, uint64_t>(cnt, ntiles, off, s_tmp);
   if (threadIdx.x == 0) *count = carry;
 }
 
@@ -4588,10 +4554,7 @@ extern "C" int rf_launch_probe_fanout(void* stream, int kind, const void* in0, c
   const dim3 g((uint32_t)nblk), b(FAN_NT);
 #define L(KD) hipLaunchKernelGGL((k_probe_fanout<KD>), g, b, 0, (hipStream_t)stream, in0, offs, key_len, seed, groups, ng, member, K, n, found)
   switch (kind) {
-    case IN_KEYS24: L(IN_KEYS24); break;
-    case IN_KEYS_W: L(IN_KEYS_W); break;
-    case IN_KEYS_B: L(IN_KEYS_B); break;
-    case IN_VAR: L(IN_VAR); break;
+    KEY_KIND_CASES(L)
     case IN_HASH: L(IN_HASH); break;
     default: return (int)hipErrorInvalidValue;
   }
@@ -4617,9 +4580,6 @@ extern "C" int rf_launch_probe_fanout(void* stream, int kind, const void* in0, c
 // requests come.
 #ifndef RF_SRV_PROF
 #define RF_SRV_PROF 0
-#endif
-#ifndef RF_SRV_PAIRSTORE
-#define RF_SRV_PAIRSTORE 1
 #endif
 __device__ __forceinline__ uint64_t srv_ld(const uint64_t* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -4708,7 +4668,6 @@ __global__ __launch_bounds__(WAVE) void k_lookup_server(const SrvReq* __restrict
             found[m] = probe_group(G, h);
           }
         }
-#if RF_SRV_PAIRSTORE
         // answers: lanes 2j and 2j+1 store the two 16-byte halves of answer j of a group of 32
         // (found, then tag, each word with its check), so one store instruction writes 1 KB of
         // consecutive answers -- whole 64-byte lines over PCIe instead of 8-byte partial writes
@@ -4730,21 +4689,6 @@ __global__ __launch_bounds__(WAVE) void k_lookup_server(const SrvReq* __restrict
             }
           }
         }
-#else
-        // (A/B: each lane stores its own answer as four 8-byte words)
-#pragma unroll
-        for (uint32_t m = 0; m < SRV_PER; m++) {
-          const uint32_t i = lane + WAVE * m;
-          if (i < k) {
-            const uint64_t ck = (uint64_t)srv_check(head + i) << 32;
-            uint64_t* r = res[(uint32_t)((head + i) & (SRV_RING - 1))].w;
-            __hip_atomic_store(r + 0, (found[m] & 0xffffffffull) | ck, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            __hip_atomic_store(r + 1, (found[m] >> 32) | ck, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            __hip_atomic_store(r + 2, (uint64_t)(uint32_t)w[m][10] | ck, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            __hip_atomic_store(r + 3, (uint64_t)(uint32_t)w[m][11] | ck, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-          }
-        }
-#endif
 #if RF_SRV_PROF
         const uint64_t pd = stamp();
         pf[0] += pb - pa;
@@ -4862,16 +4806,6 @@ extern "C" int rf_launch_probe_groups(void* stream, const uint32_t* in, const Pr
 #define CHECK_LAUNCH() do { hipError_t _e = hipGetLastError(); if (_e != hipSuccess) return (int)_e; } while (0)
 #define REC(slot) do { if (a.events && (a.ev_mask >> (slot) & 1u)) (void)hipEventRecord((hipEvent_t)a.events[slot], (hipStream_t)a.stream); } while (0)
 
-// dispatch on the input kind (template parameter of the hashing kernels)
-#define KIND_SWITCH(kind, L)           \
-  switch (kind) {                      \
-    case IN_KEYS24: L(IN_KEYS24); break; \
-    case IN_KEYS_W: L(IN_KEYS_W); break; \
-    case IN_KEYS_B: L(IN_KEYS_B); break; \
-    case IN_VAR: L(IN_VAR); break;       \
-    default: L(IN_HASH); break;          \
-  }
-
 // counts: per coarse bucket counter array (atomically accumulated); gate: see k_hash_count
 // gated launches (the fused build's spill fallback, almost never needed) use a small grid
 // that strides over the tiles: most of their cost was dispatching one workgroup per tile
@@ -4909,17 +4843,6 @@ static int launch_scatter_t(const LaunchArgs& a, EntT* ent, EntT* part, const ui
   return 0;
 }
 
-// K4m for 32-bit incremental builds (RF_AMD_K4M=0: the K4 DUAL sort instead, for A/B;
-// round-8 K4 2.22 -> 1.48 ms on one box)
-static bool k4m_enabled() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("RF_AMD_K4M");
-    v = (e && e[0] == '0') ? 0 : 1;
-  }
-  return v != 0;
-}
-
 // K4 by bitmap for the batches the planner marked (LaunchArgs::k4_bitmap); RF_AMD_K4_BITMAP=0:
 // the bucket sort instead, for A/B. g_k4_bitmap_builds counts the builds that took it
 // (rf_amd_diag_k4_bitmap_builds).
@@ -4936,35 +4859,34 @@ extern "C" uint64_t rf_k4_bitmap_builds(void) { return g_k4_bitmap_builds.load(s
 
 template <typename EntT, bool FL = (sizeof(EntT) == 8), bool DUAL = false, bool RUNS = false>
 static int launch_sort_t(const LaunchArgs& a, EntT* ent, EntT* part, const uint32_t* spill) {
-  bool launched = false;
-  if constexpr (sizeof(EntT) == 4 && !FL && !DUAL && !RUNS) {
-    if (a.k4_bitmap && k4_bitmap_enabled()) {
-      launched = true;
-      hipLaunchKernelGGL(k_cb_bitmap, dim3(a.num_cb), dim3(SORT_NT), 0, (hipStream_t)a.stream, a.plans, a.cb_filter,
-                         a.cb_count, a.cb_start, part, a.sorted32, a.idx_cnt, a.idx_start, a.outs, a.overflow, a.lis,
-                         spill);
-      g_k4_bitmap_builds.fetch_add(1, std::memory_order_relaxed);
-    }
-  }
   if constexpr (DUAL) {
-    if (k4m_enabled()) {
-      launched = true;
-      hipLaunchKernelGGL((k_cb_merge<RUNS>), dim3(a.num_cb), dim3(SORT_NT), 0, (hipStream_t)a.stream, a.plans, a.cb_filter,
-                       a.cb_count, a.cb_start, (const uint32_t*)part, a.old32, a.ob_lo, a.ob_n, a.sorted32, a.idx_cnt,
-                       a.idx_start, a.outs, a.overflow, a.lis, a.first_old, a.has_old, spill, a.cb_outs);
-      CHECK_LAUNCH();
-      // the buckets K4m handed back (bit 31 on their overflow-list entry): up to one workgroup
-      // per coarse bucket (early chain rounds hand back nearly all of them); the surplus exits
-      hipLaunchKernelGGL((k_cb_sort<EntT, FL, DUAL, true, RUNS>), dim3(a.num_cb), dim3(SORT_NT), 0, (hipStream_t)a.stream,
-                         a.plans, a.cb_filter, a.cb_count, a.cb_start, part, a.old32, a.ob_lo, a.ob_n, a.sorted32,
-                         a.idx_cnt, a.idx_start, a.outs, a.overflow, a.lis, a.first_old, a.has_old, spill, a.cb_outs,
-                         a.overflow);
+    // 32-bit incremental builds: K4m (round-8 K4 2.22 -> 1.48 ms on one box)
+    hipLaunchKernelGGL((k_cb_merge<RUNS>), dim3(a.num_cb), dim3(SORT_NT), 0, (hipStream_t)a.stream, a.plans, a.cb_filter,
+                     a.cb_count, a.cb_start, (const uint32_t*)part, a.old32, a.ob_lo, a.ob_n, a.sorted32, a.idx_cnt,
+                     a.idx_start, a.outs, a.overflow, a.lis, a.first_old, a.has_old, spill, a.cb_outs);
+    CHECK_LAUNCH();
+    // the buckets K4m handed back (bit 31 on their overflow-list entry): up to one workgroup
+    // per coarse bucket (early chain rounds hand back nearly all of them); the surplus exits
+    hipLaunchKernelGGL((k_cb_sort<EntT, FL, true, true, RUNS>), dim3(a.num_cb), dim3(SORT_NT), 0, (hipStream_t)a.stream,
+                       a.plans, a.cb_filter, a.cb_count, a.cb_start, part, a.old32, a.ob_lo, a.ob_n, a.sorted32,
+                       a.idx_cnt, a.idx_start, a.outs, a.overflow, a.lis, a.first_old, a.has_old, spill, a.cb_outs,
+                       a.overflow);
+  } else {
+    bool launched = false;
+    if constexpr (sizeof(EntT) == 4 && !FL && !RUNS) {
+      if (a.k4_bitmap && k4_bitmap_enabled()) {
+        launched = true;
+        hipLaunchKernelGGL(k_cb_bitmap, dim3(a.num_cb), dim3(SORT_NT), 0, (hipStream_t)a.stream, a.plans, a.cb_filter,
+                           a.cb_count, a.cb_start, part, a.sorted32, a.idx_cnt, a.idx_start, a.outs, a.overflow, a.lis,
+                           spill);
+        g_k4_bitmap_builds.fetch_add(1, std::memory_order_relaxed);
+      }
     }
-  }
-  if (!launched) {
-    hipLaunchKernelGGL((k_cb_sort<EntT, FL, DUAL, false, RUNS>), dim3(a.num_cb), dim3(SORT_NT), 0, (hipStream_t)a.stream, a.plans,
-                       a.cb_filter, a.cb_count, a.cb_start, part, a.old32, a.ob_lo, a.ob_n, a.sorted32, a.idx_cnt,
-                       a.idx_start, a.outs, a.overflow, a.lis, a.first_old, a.has_old, spill, a.cb_outs, nullptr);
+    if (!launched) {
+      hipLaunchKernelGGL((k_cb_sort<EntT, FL, false, false, RUNS>), dim3(a.num_cb), dim3(SORT_NT), 0, (hipStream_t)a.stream, a.plans,
+                         a.cb_filter, a.cb_count, a.cb_start, part, a.old32, a.ob_lo, a.ob_n, a.sorted32, a.idx_cnt,
+                         a.idx_start, a.outs, a.overflow, a.lis, a.first_old, a.has_old, spill, a.cb_outs, nullptr);
+    }
   }
   CHECK_LAUNCH();
   REC(EV_B_SORT);
@@ -4976,8 +4898,16 @@ static int launch_sort_t(const LaunchArgs& a, EntT* ent, EntT* part, const uint3
   return 0;
 }
 
-extern "C" int rf_launch_plines(const LaunchArgs* pa);
-static int launch_plines_list(const LaunchArgs& a);
+// the pages K6 listed in a build (k_plines_list)
+static int launch_plines_list(const LaunchArgs& a) {
+  if (!a.line_lmax || !a.num_page_slots) return 0;
+  const size_t lds = 4ull * (256 / WAVE) * (a.line_lmax + 1);
+  const uint32_t grid = a.num_page_slots < 1024 ? a.num_page_slots : 1024;
+  hipLaunchKernelGGL(k_plines_list, dim3(grid), dim3(256), lds, (hipStream_t)a.stream, a.plans, a.pg_filter,
+                     a.page_first, a.slots, a.pages, a.pg_noline, a.lines, a.line_lmax, a.lis, a.page_size);
+  CHECK_LAUNCH();
+  return 0;
+}
 
 // RUNS: a chained batch (a.tile_value / a.tile_end set): the tiles carry their run's value and
 // end, and the bucket sorts track the quirk's old entries by value (see k_cb_sort)
@@ -5109,17 +5039,6 @@ extern "C" int rf_launch_plines(const LaunchArgs* pa) {
   return 0;
 }
 
-// the pages K6 listed in a build (k_plines_list)
-static int launch_plines_list(const LaunchArgs& a) {
-  if (!a.line_lmax || !a.num_page_slots) return 0;
-  const size_t lds = 4ull * (256 / WAVE) * (a.line_lmax + 1);
-  const uint32_t grid = a.num_page_slots < 1024 ? a.num_page_slots : 1024;
-  hipLaunchKernelGGL(k_plines_list, dim3(grid), dim3(256), lds, (hipStream_t)a.stream, a.plans, a.pg_filter,
-                     a.page_first, a.slots, a.pages, a.pg_noline, a.lines, a.line_lmax, a.lis, a.page_size);
-  CHECK_LAUNCH();
-  return 0;
-}
-
 extern "C" int rf_launch_old_decode(const LaunchArgs* pa) {
   const LaunchArgs& a = *pa;
   if (a.num_old_idx == 0) return 0;
@@ -5197,10 +5116,7 @@ extern "C" int rf_launch_probe(const LaunchArgs* pa, int kind, const void* in0, 
   // 8 waves/SIMD: the line probe is bound by outstanding random line fetches (latency x
   // concurrency): 8 waves 1.14 ms, 6 waves 1.20, 5 1.27, 4 1.41 at C2 (round-1 occupancy sweep)
   switch (kind) {
-    case IN_KEYS24: PK(IN_KEYS24); break;
-    case IN_KEYS_W: PK(IN_KEYS_W); break;
-    case IN_KEYS_B: PK(IN_KEYS_B); break;
-    case IN_VAR: PK(IN_VAR); break;
+    KEY_KIND_CASES(PK)
     case IN_PAIR: PK(IN_PAIR); break;
     default: PK(IN_HASH); break;
   }

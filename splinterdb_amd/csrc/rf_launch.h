@@ -1,0 +1,84 @@
+// rf_launch.h -- every function that rf_kernels.hip defines and rf_engine.cpp calls, declared
+// once. Both files include it, so the compiler sees each declaration next to its definition:
+// extern "C" names carry no types, and a parameter changed on one side alone would still link.
+#pragma once
+#include <stdint.h>
+
+#include "rf_plan.h"
+
+extern "C" {
+
+// ---- build --------------------------------------------------------------------------------
+// K1-K6 on a.stream for one batch (a chained batch when a.tile_value is set)
+int rf_launch_build(const rf::LaunchArgs* a);
+// zero the coarse-bucket counters, the output words and the overflow / spill / page-list flags
+int rf_launch_build_init(void* stream, uint32_t* cb_count, uint32_t* cb_cursor, uint32_t num_cb,
+                         uint32_t* outs_words, uint32_t num_out_words, uint32_t* overflow, uint32_t* spill,
+                         uint32_t* plist);
+// K0: decode the old filters of an incremental add into entries
+int rf_launch_old_decode(const rf::LaunchArgs* a);
+// probe lines of a batch, cut from its image
+int rf_launch_plines(const rf::LaunchArgs* a);
+// fof[i] = the filter of element i under the prefix sums pre[0..nf]; start[i] (optional) =
+// (i - pre[fof[i]]) * mul
+int rf_launch_seg_fill(void* stream, const uint32_t* pre, uint32_t nf, uint32_t n, uint32_t* fof, uint32_t* start,
+                       uint32_t mul);
+// the probe's wave table over the run bounds runs[0..nf]: tab[w] = (filter of probe 64 w) << 7 |
+// the wave's leading probes in that filter's run
+int rf_launch_wave_tab(void* stream, const uint64_t* runs, uint32_t nf, uint64_t n, uint32_t* tab);
+// copy pages and index slots of an image to the addresses of a page table
+int rf_launch_place(void* stream, const uint8_t* img, const uint64_t* slots, uint32_t first_page, uint32_t count,
+                    uint32_t num_pages, uint32_t num_indices, uint32_t page_size, const uint64_t* table,
+                    uint32_t addrs_per_page);
+// builds whose K4 ran as the bitmap kernel, counted where K4 is launched
+uint64_t rf_k4_bitmap_builds(void);
+// diagnostics build: the buffer the build kernels write their phase clock stamps to
+int rf_debug_set_phase_buffer(uint64_t* d_buf, uint32_t kid);
+
+// ---- probes -------------------------------------------------------------------------------
+// k_probe, one lane per probe; offs: the n + 1 byte offsets of IN_VAR keys
+int rf_launch_probe(const rf::LaunchArgs* a, int kind, const void* in0, const uint64_t* offs, uint32_t key_len,
+                    const uint32_t* filter_id, uint64_t n, uint64_t* found);
+// bench.py's measured probe floor: k_probe_floor over the same runs (rf_amd_diag.h)
+int rf_launch_probe_floor(const rf::LaunchArgs* a, int kind, const void* in0, uint64_t n, uint64_t* found);
+// host-buffer lookups: n hashes, each against the group of its position
+int rf_launch_probe_groups(void* stream, const uint32_t* in, const rf::ProbeGroup* groups, uint32_t ng, uint64_t n,
+                           uint64_t* found, uint32_t* counter, uint32_t* done_flag, uint32_t seq);
+// one wave for a lookup of at most a wave of hashes
+int rf_launch_probe_small(void* stream, const rf::SmallProbe* a);
+// the persistent lookup-server wave over the request ring
+int rf_launch_lookup_server(void* stream, const rf::SrvReq* ring, rf::SrvRes* res, rf::SrvCtl* ctl, uint64_t head,
+                            uint64_t gen, uint64_t idle_ticks, uint64_t life_ticks);
+
+// ---- multi-get ----------------------------------------------------------------------------
+// offs: the n + 1 byte offsets of IN_VAR keys (in0 = their bytes), unused by the other kinds
+int rf_launch_probe_fanout(void* stream, int kind, const void* in0, const uint64_t* offs, uint32_t key_len,
+                           uint32_t seed, const rf::ProbeGroup* groups, uint32_t ng, const uint32_t* member,
+                           uint32_t K, uint64_t n, uint64_t* found);
+// diagnostics (rf_amd_diag_fanout_max_blocks): a cap on the fan-out grid; 0 = none
+void rf_fanout_set_max_blocks(uint32_t blocks);
+uint64_t rf_found_compact_tiles(uint64_t m);
+// scratch: ntiles 64-bit offsets, then ntiles 32-bit sums
+int rf_launch_found_compact(void* stream, const uint64_t* found, uint64_t m, uint64_t* cand, uint64_t cap,
+                            uint64_t* count, void* scratch);
+
+// ---- estimate, hashing, routing, verify ---------------------------------------------------
+// bitmap (zeroed by the caller, bitmap_words a multiple of 4) -> counters[0] = entries
+// decoded, counters[1] = distinct fingerprints
+int rf_launch_estimate(void* stream, const rf::EstFilter* fl, uint32_t num_filters, uint32_t total_idx, uint32_t lis,
+                       uint32_t* bitmap, uint64_t bitmap_words, uint32_t* counters);
+// out[i] = XXH32 of key i
+int rf_launch_hash(void* stream, int kind, const void* in0, const uint64_t* offs, uint32_t key_len, uint32_t seed,
+                   uint64_t n, uint32_t* out);
+uint64_t rf_route_scratch_words(uint64_t n, uint32_t world);
+// scratch: rf_route_scratch_words(n, world) u32 words; totals: world u64 (device)
+int rf_launch_route(void* stream, const uint32_t* hashes, const uint32_t* gfid, uint64_t n, const uint32_t* route,
+                    uint32_t num_g, uint32_t world, uint64_t* pairs, uint32_t* perm, uint32_t* scratch,
+                    uint64_t* totals);
+// found[perm[j]] = back[j]
+int rf_launch_unroute(void* stream, const uint64_t* back, const uint32_t* perm, uint64_t n, uint64_t* found);
+// *missing += the found words without bit `value`
+int rf_launch_count_missing(void* stream, const uint64_t* found, uint64_t n, uint32_t value,
+                            unsigned long long* missing);
+
+}  // extern "C"

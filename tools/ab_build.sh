@@ -5,7 +5,7 @@ set -e
 REV=$1; TAG=$2; DEFS=$3; D=$(mktemp -d)
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 mkdir -p $D/splinterdb_amd/csrc $D/include
-for f in splinterdb_amd/csrc/rf_kernels.hip splinterdb_amd/csrc/rf_engine.cpp splinterdb_amd/csrc/rf_device.h splinterdb_amd/csrc/rf_plan.h splinterdb_amd/csrc/rf_batch_plan.h include/rf_amd.h include/rf_amd_diag.h; do
+for f in splinterdb_amd/csrc/rf_kernels.hip splinterdb_amd/csrc/rf_engine.cpp splinterdb_amd/csrc/rf_device.h splinterdb_amd/csrc/rf_plan.h splinterdb_amd/csrc/rf_batch_plan.h splinterdb_amd/csrc/rf_launch.h include/rf_amd.h include/rf_amd_diag.h; do
   if [ "$REV" = WT ]; then cp $ROOT/$f $D/$f
   elif git -C $ROOT cat-file -e $REV:$f 2>/dev/null; then git -C $ROOT show $REV:$f > $D/$f   # (a header the revision predates: skipped)
   fi

@@ -1,7 +1,7 @@
 """Diagnostic (not a test): fuzz case 24's incremental add (fp 26, lis 5, 33,825 old + 16,912 new
 hashes, value 23) built by the engine and by the oracle; prints where the images differ (first
-differing slots / page bytes, and the coarse bucket of the index) -- RF_AMD_K4M=0/1 decides
-which bucket sort the engine uses."""
+differing slots / page bytes, and the coarse bucket of the index). The engine sorts the
+buckets with K4m (k_cb_merge and its hand-back list)."""
 import os
 import sys
 
@@ -25,8 +25,7 @@ b2.build_hashes(dev(h2))
 img = b2.image(0)
 of = O.filter_add(ocfg, h1, value=23)
 of2 = O.filter_add(ocfg, h2, value=23, old=of)
-print("K4M", os.environ.get("RF_AMD_K4M", "1"), "unique", img.num_unique, of2.num_unique, "pages", img.num_pages,
-      of2.num_pages)
+print("unique", img.num_unique, of2.num_unique, "pages", img.num_pages, of2.num_pages)
 os_ = of2.slots()[: of2.num_indices]
 ds = np.flatnonzero(img.slots != os_)
 print("slots differ:", ds.size, "first", ds[:8].tolist(), "cb(128 idx)", sorted(set((ds // 128).tolist()))[:16])
