@@ -69,6 +69,12 @@ const char *rf_amd_last_error(void);
  * per filter, a previously built filter (batch, index) whose entries are merged in
  * (routing_filter_add's old_filter, src/routing_filter.c:355-368, 496-544); pass
  * old_batch[f] = NULL for a fresh filter.
+ * A filter built on a rejected old filter (one whose rf_amd_filter_info.error is set) is itself
+ * rejected: its error holds the old filter's bits besides its own, it finds nothing, and its
+ * build reads neither the old filter's slots nor its pages (a rejected filter has none). The
+ * rule is applied on the device, in stream order, so create does not wait for the old filter's
+ * build and returns OK; the bits show in rf_amd_batch_info after the build. It holds for
+ * rf_amd_batch_create_runs and for a trimmed old batch alike.
  */
 int rf_amd_batch_create(rf_amd_engine *e, const rf_amd_config *cfg, uint32_t num_filters,
                         const uint32_t *num_new, const uint16_t *value,

@@ -545,6 +545,7 @@ static void fill_old_pointers(rf_amd_batch* b, rf_amd_batch* const* old_batch, c
     FilterPlan& p = b->plans[f];
     p.old_pages = ob->d_pages.as<uint8_t>() + (uint64_t)op->page_base * b->cfg.page_size;
     p.old_slots = ob->d_slots.as<uint64_t>() + op->idx_base;
+    p.old_out = ob->d_outs.as<FilterOut>() + (old_index ? old_index[f] : 0);
     if (!p.old_direct) continue;
     const uint32_t* es = ob->wide ? ob->d_sorted.as<uint32_t>() : ob->d_part.as<uint32_t>();
     p.old_entries = es + op->e_first;

@@ -1772,7 +1772,7 @@ __global__ __launch_bounds__(LAYOUT_NT) void k_layout(const FilterPlan* __restri
   if (layout_groups(P, seg) > 1) return;  // laid out by k_layout_seg's workgroups
   clean_counters(clean, P, f, 0, 1);      // before any return below
   DBG_PHASE_K(4, 15);
-  if (threadIdx.x == 0) s_err = 0;
+  if (threadIdx.x == 0) s_err = old_error(P);  // a filter built on a rejected one is rejected
   __syncthreads();
   // sizes -> exclusive prefix (element j = k * LAYOUT_NT + thread: coalesced loads)
   // every count load first, from a clamped index (no branch around a load: each branch
@@ -2089,7 +2089,7 @@ __global__ __launch_bounds__(LAYOUT_NT) void k_layout_seg(const FilterPlan* __re
   const uint32_t L = seg + H;  // blocks in the window; the last segment's ends at n
   uint8_t* s_mark = reinterpret_cast<uint8_t*>(s_mark32);
   DBG_PHASE_K(4, 15);
-  if (threadIdx.x == 0) s_err = 0;
+  if (threadIdx.x == 0) s_err = old_error(P);  // every segment of a filter built on a rejected one fails
   for (uint32_t i = threadIdx.x; i < LAYOUT_SEG_MAX / 4; i += LAYOUT_NT) s_mark32[i] = 0;
   // sizes (k-major: coalesced loads, every load before the first use), then one scan over
   // each thread's LSEG_PERC consecutive elements
@@ -2850,12 +2850,18 @@ __global__ __launch_bounds__(ASM_NT) __attribute__((amdgpu_waves_per_eu(8))) voi
 // ======================================================================================
 // Every old index of the batch in one list (filter f's at P.old_idx_base ..): the decode of
 // all old filters is three launches, whatever the number of filters.
-// k_old_counts: per old index, num_remainders from its header -> cnt
+// k_old_counts: per old index, num_remainders from its header -> cnt. A rejected old filter has
+// no headers (its slots and pages were never written): its indices count as empty, and K5
+// rejects the filter built on it (old_error)
 __global__ void k_old_counts(const FilterPlan* __restrict__ plans, const uint32_t* __restrict__ old_idx_filter,
                              uint32_t num_old_idx, uint32_t* __restrict__ cnt) {
   const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= num_old_idx) return;
   const FilterPlan& P = plans[old_idx_filter[g]];
+  if (old_error(P)) {
+    cnt[g] = 0;
+    return;
+  }
   const uint64_t s = P.old_slots[g - P.old_idx_base];
   cnt[g] = (uint32_t)P.old_pages[s] | ((uint32_t)P.old_pages[s + 1] << 8);
 }
@@ -2916,6 +2922,7 @@ __global__ __launch_bounds__(256) void k_old_decode(const FilterPlan* __restrict
   const uint32_t lane = threadIdx.x & (WAVE - 1);
   if (g >= num_old_idx) return;  // uniform per wave
   const FilterPlan& P = plans[old_idx_filter[g]];
+  if (old_error(P)) return;                 // rejected old filter: k_old_counts counted nothing
   const uint32_t wid = g - P.old_idx_base;  // old index within its filter
   const uint32_t index_size = 1u << lis;
   const uint64_t hdr = P.old_slots[wid];
@@ -2984,6 +2991,11 @@ __global__ __launch_bounds__(256) void k_old_cb_bounds(const FilterPlan* __restr
   const uint32_t f = cb_filter[cb];
   const FilterPlan& P = plans[f];
   const uint32_t cl = cb - P.cb_base, ncb = 1u << P.cbits;
+  if (old_error(P)) {  // rejected old filter: no old entries, in place or decoded
+    ob_lo[cb] = 0;
+    ob_n[cb] = 0;
+    return;
+  }
   if (P.old_direct) {
     // new coarse bucket cl lies in the old filter's coarse bucket cl >> (cbits - old_cbits), whose
     // entries are those of its indices [c_old * ipc, (c_old + 1) * ipc), consecutive in its entry

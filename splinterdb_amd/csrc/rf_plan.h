@@ -54,6 +54,13 @@ inline int fixed_kind(const void* p, uint32_t key_len) {
 constexpr uint32_t ERR_INDEX_OVERFLOW = 1u, ERR_BLOCK_TOO_BIG = 2u, ERR_PAGE_CAP = 4u,
                    ERR_GEOMETRY = 8u;
 
+struct FilterOut {
+  uint32_t num_unique;
+  uint32_t num_pages;
+  uint32_t error;
+  uint32_t pad;
+};
+
 struct FilterPlan {
   uint64_t e_first;    // first entry slot of this filter in the entry arrays
   uint64_t key_first;  // first input (key / hash) of this filter's new fingerprints
@@ -94,7 +101,13 @@ struct FilterPlan {
   const uint32_t* old_entries;
   const uint32_t* old_idx_start;
   const uint32_t* old_idx_cnt;
+  // The old filter's build result in its own batch (null: no old filter). A rejected filter
+  // (error != 0) has no slots, pages or lines, so a filter built on it reads none of them: its
+  // old entries count as none, and K5 takes the old bits over as its own (old_error).
+  const FilterOut* old_out;
 };
+// the error bits of the filter P is built on (device: its build is ordered before P's)
+__host__ __device__ inline uint32_t old_error(const FilterPlan& P) { return P.old_out ? P.old_out->error : 0u; }
 
 // K5 (page layout) workgroups of a filter: `seg` indices each when the filter has more than
 // that. seg is a power of two in [256, LAYOUT_SEG_MAX] or 0 (never split); the put-back
@@ -177,13 +190,6 @@ struct SmallProbe {
   ProbeGroup groups[SMALL_GROUPS];
   uint64_t* found;      // pinned host memory
   uint32_t* done_flag;  // pinned host memory: seq once every result is visible
-};
-
-struct FilterOut {
-  uint32_t num_unique;
-  uint32_t num_pages;
-  uint32_t error;
-  uint32_t pad;
 };
 
 struct LaunchArgs {

@@ -244,6 +244,10 @@ def load_library(build_if_missing=True):
     L.rf_amd_filter_lookup_var_keys.argtypes = [vp, ctypes.POINTER(RfConfig), ctypes.POINTER(RfImage),
                                                 vp, vp, u64, vp]
     L.rf_amd_diag_fanout_max_blocks.argtypes = [u32]
+    L.rf_amd_host_alloc.argtypes = [vp, u64, ctypes.POINTER(vp)]
+    L.rf_amd_host_free.argtypes = [vp, vp]
+    L.rf_amd_host_free.restype = None
+    L.rf_amd_batch_place_image.argtypes = [vp, u32, vp, u32, u32, u32, i32, u32, vp]
     _lib = L
     return L
 

@@ -288,7 +288,11 @@ static void check_old_filters() {
   CHECK(b.plans[0].old_region == 5000 && b.plans[0].num_fp == 5100 && b.plans[0].npo == 1);
   CHECK(b.num_old_tiles == 1 && b.pre_of(PRE_OTILE)[1] == 1);
   CHECK(b.plans[0].old_pages == nullptr && b.plans[0].old_slots == nullptr && b.plans[0].old_entries == nullptr &&
-        b.plans[0].old_idx_start == nullptr && b.plans[0].old_idx_cnt == nullptr);  // the engine's to fill in
+        b.plans[0].old_idx_start == nullptr && b.plans[0].old_idx_cnt == nullptr &&
+        b.plans[0].old_out == nullptr);  // the engine's to fill in
+  // the planner does not (and cannot) tell a rejected old filter from a healthy one: its error
+  // bits are on the device, perhaps still to be written; the kernels test them (old_error)
+  CHECK(old_error(b.plans[0]) == 0);
   PlanKnobs k;
   k.old_decode = true;
   CHECK(plan1(cfg, 100, 1, &b, &o, k) == 0);
