@@ -292,8 +292,11 @@ int rf_amd_host_unregister(rf_amd_engine *e, void *p);
  * of the num_pages image pages (inside registered memory), then each page's disk address,
  * then the destinations of the ceil(num_indices / addrs_per_page) index pages. One call writes
  * pages [first_page, first_page + count) and, with_index, the absolute index slots; the
- * destinations it uses are translated in place. Stream-ordered (NULL: the engine stream):
- * wait with rf_amd_engine_fence before using the pages */
+ * destinations it uses are translated in place (so the ranges of successive calls on one
+ * table are disjoint). A refused call (EINVAL: a destination outside the registered ranges,
+ * pages outside the filter, addrs_per_page 0 or over page_size / 8, f out of range) writes
+ * nothing and leaves the table unchanged. Stream-ordered (NULL: the engine stream): wait with
+ * rf_amd_engine_fence before using the pages */
 int rf_amd_batch_place_image(rf_amd_batch *b, uint32_t f, uint64_t *table, uint32_t num_pages,
                              uint32_t first_page, uint32_t count, int with_index, uint32_t addrs_per_page,
                              void *stream);

@@ -42,6 +42,14 @@ int rf_amd_debug_phase_buffer(void *d_buf, uint32_t kernel);
  * the counters after reading them. */
 int rf_amd_diag_lookup_stats(uint64_t *out, int reset);
 
+/* which way those round trips went, counted where the call decides: out[0] small (hashes and
+ * filter descriptors in the kernel arguments), out[1] mapped (the kernel reads the slot's pinned
+ * buffer), out[2] copy (one H2D copy first); out[3] those that waited by synchronising the
+ * stream (RF_AMD_PROBE_WAIT=sync) instead of polling the completion word. A call with no probes
+ * or no groups decides nothing and is not counted. reset != 0 zeroes the counters after reading
+ * them. */
+int rf_amd_diag_lookup_paths(uint64_t *out, int reset);
+
 /* the lookup server so far: out[0] tickets issued, out[1] server launches, out[2] the first
  * ticket the last exited server did not serve */
 int rf_amd_lookup_server_stats(rf_amd_engine *e, uint64_t *out);

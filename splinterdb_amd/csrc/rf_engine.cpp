@@ -874,10 +874,17 @@ extern "C" int rf_amd_batch_place_image(rf_amd_batch* b, uint32_t f, uint64_t* t
       }
       return false;
     };
-    for (uint32_t k = first_page; k < first_page + count; k++)
-      if (!xlate(table[k], P)) return fail(RF_AMD_EINVAL, "page destination outside the registered ranges");
-    for (uint32_t k = 0; k < nip; k++)
-      if (!xlate(table[2ull * num_pages + k], P)) return fail(RF_AMD_EINVAL, "index page outside the registered ranges");
+    // a refused call leaves the table as it was: check every destination, then translate
+    for (uint32_t k = first_page; k < first_page + count; k++) {
+      uint64_t w = table[k];
+      if (!xlate(w, P)) return fail(RF_AMD_EINVAL, "page destination outside the registered ranges");
+    }
+    for (uint32_t k = 0; k < nip; k++) {
+      uint64_t w = table[2ull * num_pages + k];
+      if (!xlate(w, P)) return fail(RF_AMD_EINVAL, "index page outside the registered ranges");
+    }
+    for (uint32_t k = first_page; k < first_page + count; k++) (void)xlate(table[k], P);
+    for (uint32_t k = 0; k < nip; k++) (void)xlate(table[2ull * num_pages + k], P);
   }
   void* dt = nullptr;
   HIPCHK(hipSetDevice(e->device));
@@ -1807,6 +1814,9 @@ extern "C" int rf_amd_lookup_server_stats(rf_amd_engine* e, uint64_t* out) {
 // ns before the launch (slot, buffers, build ordering, argument packing), ns in the launch
 // call, ns waiting for the completion word (and copying the results out)
 static std::atomic<uint64_t> g_lk_calls{0}, g_lk_prep_ns{0}, g_lk_launch_ns{0}, g_lk_wait_ns{0};
+// which way probe_groups_host sent its round trips (rf_amd_diag_lookup_paths): small, mapped,
+// copy, and how many of them waited by synchronising the stream
+static std::atomic<uint64_t> g_lk_small{0}, g_lk_mapped{0}, g_lk_copy{0}, g_lk_sync{0};
 static inline uint64_t mono_ns() {
   timespec ts;
   clock_gettime(CLOCK_MONOTONIC, &ts);
@@ -1839,6 +1849,13 @@ extern "C" int rf_amd_diag_lookup_stats(uint64_t* out, int reset) {
   return 0;
 }
 
+extern "C" int rf_amd_diag_lookup_paths(uint64_t* out, int reset) {
+  if (!out) return fail(RF_AMD_EINVAL, "null output");
+  std::atomic<uint64_t>* c[4] = {&g_lk_small, &g_lk_mapped, &g_lk_copy, &g_lk_sync};
+  for (int k = 0; k < 4; k++) out[k] = reset ? c[k]->exchange(0) : c[k]->load();
+  return 0;
+}
+
 static int probe_groups_host(rf_amd_engine* e, const std::vector<ProbeGroup>& groups,
                              const uint32_t* h_hashes, const uint32_t* h_group, uint64_t n, uint64_t* h_found) {
   if (n == 0) return 0;
@@ -1850,6 +1867,8 @@ static int probe_groups_host(rf_amd_engine* e, const std::vector<ProbeGroup>& gr
   const size_t o_g = (8 * n + 15) & ~15ull, o_f = (o_g + sizeof(ProbeGroup) * ng + 63) & ~63ull;
   const bool small = small_ok && wait != 2 && n <= SMALL_PROBES && ng <= SMALL_GROUPS;
   const bool mapped = mode == 1 || (mode == 0 && n <= MAPPED_MAX_PROBES);
+  (small ? g_lk_small : mapped ? g_lk_mapped : g_lk_copy).fetch_add(1, std::memory_order_relaxed);
+  if (!small && wait == 2) g_lk_sync.fetch_add(1, std::memory_order_relaxed);
   ProbeSlot* s = slot_take(e);
   if (!s) return RF_AMD_ENOMEM;
   struct Give {

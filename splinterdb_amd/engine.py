@@ -61,7 +61,7 @@ EXPORTED = [
     "rf_amd_filter_set_probe_keys", "rf_amd_filter_set_probe_hashes",
     "rf_amd_found_compact_scratch_bytes", "rf_amd_found_compact",
     "rf_amd_filter_set_probe_var_keys", "rf_amd_batch_probe_var_keys_runs", "rf_amd_filter_lookup_var_keys",
-    "rf_amd_diag_fanout_max_blocks",
+    "rf_amd_diag_fanout_max_blocks", "rf_amd_diag_lookup_paths",
 ]
 ROUTE_MAX_WORLD = 16
 FOUND_COMPACT_TILE = 4096  # found words per workgroup of rf_amd_found_compact (FC_TILE)
@@ -155,6 +155,7 @@ def load_library(build_if_missing=True):
     L.rf_amd_debug_phase_buffer.argtypes = [vp, u32]
     L.rf_amd_debug_probe_floor.argtypes = [vp, vp, u32, vp, vp, vp]
     L.rf_amd_diag_lookup_stats.argtypes = [vp, ctypes.c_int]
+    L.rf_amd_diag_lookup_paths.argtypes = [vp, ctypes.c_int]
     L.rf_amd_lookup_submit.argtypes = [vp, vp, u32, u32, vp, ctypes.POINTER(u64)]
     L.rf_amd_lookup_wait.argtypes = [vp, u64, ctypes.POINTER(u64)]
     L.rf_amd_lookup_reap.argtypes = [vp, vp, vp, u64]
@@ -248,6 +249,10 @@ def load_library(build_if_missing=True):
     L.rf_amd_host_free.argtypes = [vp, vp]
     L.rf_amd_host_free.restype = None
     L.rf_amd_batch_place_image.argtypes = [vp, u32, vp, u32, u32, u32, i32, u32, vp]
+    L.rf_amd_host_register.argtypes = [vp, vp, u64]
+    L.rf_amd_host_unregister.argtypes = [vp, vp]
+    L.rf_amd_engine_fence.argtypes = [vp, ctypes.POINTER(u64)]
+    L.rf_amd_engine_fence_wait.argtypes = [vp, u64]
     _lib = L
     return L
 
