@@ -72,6 +72,12 @@ int rf_amd_diag_lookup_server_kill(rf_amd_engine *e, int err, uint32_t gap_us);
  * see which of the two the build took */
 uint64_t rf_amd_diag_k4_bitmap_builds(void);
 
+/* how many builds of this process partitioned their keys as 16-bit in-bucket keys, the format
+ * the bitmap kernel reads when the partition did not spill, instead of 32-bit entries. The host
+ * decides both at once, so the two counters advance together; a build that takes the bucket
+ * sort leaves both unchanged */
+uint64_t rf_amd_diag_part16_builds(void);
+
 /* process-wide cap on the grid of the fan-out probe (rf_amd_filter_set_probe_*), in workgroups
  * of 256 keys; 0 restores the default, a grid that covers n. With a cap below n / 256 every
  * wave takes several 64-key chunks, so a test of a few thousand keys runs the kernel's

@@ -1841,6 +1841,7 @@ struct LookupClock {
 extern "C" const char* rf_amd_build_id(void) { return RF_AMD_SRC_ID; }
 
 extern "C" uint64_t rf_amd_diag_k4_bitmap_builds(void) { return rf_k4_bitmap_builds(); }
+extern "C" uint64_t rf_amd_diag_part16_builds(void) { return rf_part16_builds(); }
 
 extern "C" int rf_amd_diag_lookup_stats(uint64_t* out, int reset) {
   if (!out) return fail(RF_AMD_EINVAL, "null output");

@@ -413,7 +413,12 @@ extern "C" int rf_debug_set_phase_buffer(uint64_t* d_buf, uint32_t kid) {
 #endif
 // FL (32-bit incremental builds): the entries are written flagged new, (e << 1) | 1.
 // RUNS (chained batches): the tile's value and end come from its run (TileRuns).
-template <int KIND, bool FL = false, bool RUNS = false>
+// P16 (fresh single-run builds whose K4 is k_cb_bitmap, which uses an entry's low 16 bits
+// only): the copy-out stores those 16 bits, packed from the same region base, so the region
+// stores and K4's reads are half the bytes. The staging stays 32-bit (the copy-out takes the
+// bucket from the staged entry). After a spill the gated kernels rewrite `part` as 32-bit
+// entries, as for any build.
+template <int KIND, bool FL = false, bool RUNS = false, bool P16 = false>
 __global__ __launch_bounds__(SCAT_NT) __attribute__((amdgpu_waves_per_eu(RF_SCAT_WPE))) void k_hash_scatter(const FilterPlan* __restrict__ plans,
                                                           const uint32_t* __restrict__ tile_filter,
                                                           const uint32_t* __restrict__ tile_start,
@@ -428,6 +433,7 @@ __global__ __launch_bounds__(SCAT_NT) __attribute__((amdgpu_waves_per_eu(RF_SCAT
   __shared__ uint32_t s_tmp[SCAT_NT / WAVE + 1];
   constexpr int PER = TILE_KEYS / SCAT_NT;
   constexpr int BPT = MAX_CB / SCAT_NT;
+  static_assert(!P16 || (!FL && !RUNS), "16-bit keys: fresh single-run builds only");
   DBG_PHASE_K(2, 15);
   const uint32_t t = xcd_chunk(blockIdx.x, gridDim.x);  // a filter's tiles share an XCD
   const FilterPlan& P = plans[tile_filter[t]];
@@ -607,11 +613,23 @@ __global__ __launch_bounds__(SCAT_NT) __attribute__((amdgpu_waves_per_eu(RF_SCAT
   __syncthreads();
   DBG_PHASE_K(2, 4);
   uint32_t* dst = part + P.e_first;
-  for (uint32_t j = threadIdx.x; j < total; j += SCAT_NT) {
-    const uint32_t x = s_stage[j];
-    const uint32_t cb = cb_of(x);
-    const uint32_t slot = s_off[cb] + j;  // position inside the bucket's region
-    if (slot < (uint32_t)SORT_CAP) dst[(uint64_t)cb * CB_REGION + slot] = x;
+  if constexpr (P16) {
+    // the in-bucket key alone, 16 bits per slot from the region's base (k_cb_bitmap masks it
+    // to the filter's key width and restores the bits above from the bucket's number)
+    auto reg16 = [&](uint32_t cb) -> uint16_t* { return reinterpret_cast<uint16_t*>(dst + (uint64_t)cb * CB_REGION); };
+    for (uint32_t j = threadIdx.x; j < total; j += SCAT_NT) {
+      const uint32_t x = s_stage[j];
+      const uint32_t cb = cb_of(x);
+      const uint32_t slot = s_off[cb] + j;  // position inside the bucket's region
+      if (slot < (uint32_t)SORT_CAP) reg16(cb)[slot] = (uint16_t)x;
+    }
+  } else {
+    for (uint32_t j = threadIdx.x; j < total; j += SCAT_NT) {
+      const uint32_t x = s_stage[j];
+      const uint32_t cb = cb_of(x);
+      const uint32_t slot = s_off[cb] + j;  // position inside the bucket's region
+      if (slot < (uint32_t)SORT_CAP) dst[(uint64_t)cb * CB_REGION + slot] = x;
+    }
   }
   DBG_PHASE_K(2, 8);
 }
@@ -1120,7 +1138,10 @@ __global__ __launch_bounds__(SORT_NT, 6) void k_cb_sort(const FilterPlan* __rest
 // - 5, so its start and count are two reads of those prefixes. All entries carry one value, so
 // kept entries have distinct fingerprints, none of them UINT32_MAX >> vs (fp_size + vs < 32):
 // the bucket adds `kept` to num_unique. No ranks, bins, sorting networks or dedupe pass.
-// Same inputs, outputs and grid as k_cb_sort<uint32_t, false, false, false, false>.
+// Same outputs and grid as k_cb_sort<uint32_t, false, false, false, false>; the input is the
+// partition's 16-bit keys (k_hash_scatter P16: the host takes both decisions at once), or, after
+// a spill, 32-bit entries at the scanned starts. The sorted entries written over the bucket's
+// own region stay 32-bit; every key of the region is in registers before the first store.
 __global__ __launch_bounds__(SORT_NT, 8) void k_cb_bitmap(const FilterPlan* __restrict__ plans,
                                                           const uint32_t* __restrict__ cb_filter,
                                                           const uint32_t* __restrict__ cb_count,
@@ -1146,30 +1167,57 @@ __global__ __launch_bounds__(SORT_NT, 8) void k_cb_bitmap(const FilterPlan* __re
   const uint32_t n = cb_count[cb];
   const uint32_t cbl = cb - P.cb_base;
   // fused build without spill: fixed SORT_CAP regions; otherwise the scanned starts
-  const uint32_t cb_rel = (spill && *spill == 0) ? cbl * CB_REGION : cb_start[cb];
+  // (the partition of such a build wrote 16-bit keys, k_hash_scatter P16; after a spill the
+  // gated kernels rewrote `part` as 32-bit entries)
+  const bool keys16 = spill && *spill == 0;  // workgroup-uniform
+  const uint32_t cb_rel = keys16 ? cbl * CB_REGION : cb_start[cb];
   if (n > SORT_CAP) {  // handled by k_cb_sort_big
     if (threadIdx.x == 0) overflow[1 + atomicAdd(&overflow[0], 1u)] = cb;
     return;
   }
   const uint32_t kw = P.bbits + P.rvs, kmask = (1u << kw) - 1u;
   // the bucket's entry loads go out first (clamped, branch-free) and land while the bitmap is
-  // cleared; the barrier after the clearing orders only LDS
+  // cleared; the barrier after the clearing orders only LDS. 16-bit keys are read as pairs,
+  // half as many loads (the last pair of an odd n carries one stale key, not used)
+  constexpr int PER2 = PER / 2;
+  static_assert(PER % 2 == 0, "a thread's keys in pairs");
   uint32_t v[PER];
   const uint32_t* src = part + P.e_first + cb_rel;
-  const uint32_t nm1 = n ? n - 1 : 0u;
+  if (keys16) {
+    const uint32_t pm1 = n ? (n - 1) >> 1 : 0u;
 #pragma unroll
-  for (int k = 0; k < PER; k++) v[k] = src[min(threadIdx.x + k * SORT_NT, nm1)];
+    for (int k = 0; k < PER2; k++) v[k] = src[min(threadIdx.x + k * SORT_NT, pm1)];
+  } else {
+    const uint32_t nm1 = n ? n - 1 : 0u;
+#pragma unroll
+    for (int k = 0; k < PER; k++) v[k] = src[min(threadIdx.x + k * SORT_NT, nm1)];
+  }
   v4u* bm4 = reinterpret_cast<v4u*>(s_bm) + threadIdx.x;
   *bm4 = v4u{0u, 0u, 0u, 0u};
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
   __builtin_amdgcn_s_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
   DBG_PHASE(0);
+  if (keys16) {
 #pragma unroll
-  for (int k = 0; k < PER; k++) {
-    if (threadIdx.x + k * SORT_NT < n) {
-      const uint32_t key = v[k] & kmask;
-      atomicOr(&s_bm[key >> 5], 1u << (key & 31u));
+    for (int k = 0; k < PER2; k++) {
+      const uint32_t i = 2u * (threadIdx.x + k * SORT_NT);
+      if (i < n) {
+        const uint32_t key = v[k] & kmask;
+        atomicOr(&s_bm[key >> 5], 1u << (key & 31u));
+      }
+      if (i + 1 < n) {
+        const uint32_t key = (v[k] >> 16) & kmask;
+        atomicOr(&s_bm[key >> 5], 1u << (key & 31u));
+      }
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < PER; k++) {
+      if (threadIdx.x + k * SORT_NT < n) {
+        const uint32_t key = v[k] & kmask;
+        atomicOr(&s_bm[key >> 5], 1u << (key & 31u));
+      }
     }
   }
   __syncthreads();
@@ -4857,7 +4905,8 @@ static int launch_scatter_t(const LaunchArgs& a, EntT* ent, EntT* part, const ui
 
 // K4 by bitmap for the batches the planner marked (LaunchArgs::k4_bitmap); RF_AMD_K4_BITMAP=0:
 // the bucket sort instead, for A/B. g_k4_bitmap_builds counts the builds that took it
-// (rf_amd_diag_k4_bitmap_builds).
+// (rf_amd_diag_k4_bitmap_builds). launch_build_t decides once per build, for the partition (16-bit
+// keys out, g_part16_builds) and for K4 together.
 static bool k4_bitmap_enabled() {
   static int v = -1;
   if (v < 0) {
@@ -4868,9 +4917,12 @@ static bool k4_bitmap_enabled() {
 }
 static std::atomic<uint64_t> g_k4_bitmap_builds{0};
 extern "C" uint64_t rf_k4_bitmap_builds(void) { return g_k4_bitmap_builds.load(std::memory_order_relaxed); }
+static std::atomic<uint64_t> g_part16_builds{0};
+extern "C" uint64_t rf_part16_builds(void) { return g_part16_builds.load(std::memory_order_relaxed); }
 
+// bitmap: K4 as k_cb_bitmap (fresh single-run 32-bit builds only; the partition wrote 16-bit keys)
 template <typename EntT, bool FL = (sizeof(EntT) == 8), bool DUAL = false, bool RUNS = false>
-static int launch_sort_t(const LaunchArgs& a, EntT* ent, EntT* part, const uint32_t* spill) {
+static int launch_sort_t(const LaunchArgs& a, EntT* ent, EntT* part, const uint32_t* spill, bool bitmap = false) {
   if constexpr (DUAL) {
     // 32-bit incremental builds: K4m (round-8 K4 2.22 -> 1.48 ms on one box)
     hipLaunchKernelGGL((k_cb_merge<RUNS>), dim3(a.num_cb), dim3(SORT_NT), 0, (hipStream_t)a.stream, a.plans, a.cb_filter,
@@ -4886,7 +4938,7 @@ static int launch_sort_t(const LaunchArgs& a, EntT* ent, EntT* part, const uint3
   } else {
     bool launched = false;
     if constexpr (sizeof(EntT) == 4 && !FL && !RUNS) {
-      if (a.k4_bitmap && k4_bitmap_enabled()) {
+      if (bitmap) {
         launched = true;
         hipLaunchKernelGGL(k_cb_bitmap, dim3(a.num_cb), dim3(SORT_NT), 0, (hipStream_t)a.stream, a.plans, a.cb_filter,
                            a.cb_count, a.cb_start, part, a.sorted32, a.idx_cnt, a.idx_start, a.outs, a.overflow, a.lis,
@@ -4986,14 +5038,28 @@ static int launch_build_t(const LaunchArgs& a) {
     // fresh build: fused hash + partition into fixed regions (cb_count = fills)
     uint32_t* ent = (uint32_t*)a.ent;
     uint32_t* part = (uint32_t*)a.part;
+    // K4 by bitmap reads an entry's low 16 bits only, so the partition of such a build writes
+    // only those: one decision for both launches
+    bool bitmap = false;
+    if constexpr (!RUNS) bitmap = a.k4_bitmap && k4_bitmap_enabled();
     if (a.num_tiles) {
-#define L(K) hipLaunchKernelGGL((k_hash_scatter<K, false, RUNS>), dim3(a.num_tiles), dim3(SCAT_NT), 0, (hipStream_t)a.stream, \
+#define L(K) hipLaunchKernelGGL((k_hash_scatter<K, false, RUNS, P16>), dim3(a.num_tiles), dim3(SCAT_NT), 0, (hipStream_t)a.stream, \
                                 a.plans, a.tile_filter, a.tile_start, a.in0, a.offs, a.key_len, a.fp_size, a.seed, \
                                 part, a.cb_count, a.spill, runs)
-      KIND_SWITCH(a.kind, L);
+      if constexpr (!RUNS) {
+        if (bitmap) {
+          constexpr bool P16 = true;
+          KIND_SWITCH(a.kind, L);
+        }
+      }
+      if (!bitmap) {
+        constexpr bool P16 = false;
+        KIND_SWITCH(a.kind, L);
+      }
 #undef L
       CHECK_LAUNCH();
     }
+    if (bitmap) g_part16_builds.fetch_add(1, std::memory_order_relaxed);
     REC(EV_B_HASH);
     // spill fallback (both kernels return at once unless *spill): exact counts into cb_cursor
     // and, by the last workgroup to finish them, their scan -> cb_count / cb_start / cb_cursor
@@ -5007,7 +5073,7 @@ static int launch_build_t(const LaunchArgs& a) {
     REC(EV_B_SCAN);
     if (int rc = launch_scatter_t<uint32_t, false, RUNS>(a, ent, part, a.spill)) return rc;
     REC(EV_B_SCATTER);
-    if (int rc = launch_sort_t<uint32_t, false, false, RUNS>(a, ent, part, a.spill)) return rc;
+    if (int rc = launch_sort_t<uint32_t, false, false, RUNS>(a, ent, part, a.spill, bitmap)) return rc;
   }
   // the build's counters left zero for the next build (a.self_clean: fresh builds)
   const BuildClean clean = a.self_clean ? BuildClean{a.cb_count, a.cb_cursor, a.overflow, a.spill}

@@ -32,6 +32,8 @@ int rf_launch_place(void* stream, const uint8_t* img, const uint64_t* slots, uin
                     uint32_t addrs_per_page);
 // builds whose K4 ran as the bitmap kernel, counted where K4 is launched
 uint64_t rf_k4_bitmap_builds(void);
+// builds whose partition wrote 16-bit in-bucket keys for that kernel (k_hash_scatter, P16)
+uint64_t rf_part16_builds(void);
 // diagnostics build: the buffer the build kernels write their phase clock stamps to
 int rf_debug_set_phase_buffer(uint64_t* d_buf, uint32_t kid);
 

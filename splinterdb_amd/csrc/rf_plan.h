@@ -31,6 +31,9 @@ constexpr uint32_t CB_REGION = SORT_CAP + RF_REGION_PAD;
 // K4 by bitmap (k_cb_bitmap): fresh builds whose entries differ, inside a coarse bucket, only in
 // their low bbits + rvs bits are sorted and deduplicated as a set of that many bits in LDS
 constexpr uint32_t K4_BITMAP_MAX_BITS = 16;  // 2^16 bits = 8 KiB, one 16-byte access per thread
+// Such a build's partition writes each entry's low 16 bits only (k_hash_scatter, P16), packed
+// from the region's unchanged base, and k_cb_bitmap reads them two to a 32-bit word
+static_assert(SORT_CAP % 2 == 0, "16-bit keys are stored and read in pairs");
 constexpr int BIG_NT = 1024;
 constexpr int BIG_GRID = 64;
 constexpr int LAYOUT_NT = 1024;

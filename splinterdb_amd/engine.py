@@ -61,7 +61,7 @@ EXPORTED = [
     "rf_amd_filter_set_probe_keys", "rf_amd_filter_set_probe_hashes",
     "rf_amd_found_compact_scratch_bytes", "rf_amd_found_compact",
     "rf_amd_filter_set_probe_var_keys", "rf_amd_batch_probe_var_keys_runs", "rf_amd_filter_lookup_var_keys",
-    "rf_amd_diag_fanout_max_blocks", "rf_amd_diag_lookup_paths",
+    "rf_amd_diag_fanout_max_blocks", "rf_amd_diag_lookup_paths", "rf_amd_diag_part16_builds",
 ]
 ROUTE_MAX_WORLD = 16
 FOUND_COMPACT_TILE = 4096  # found words per workgroup of rf_amd_found_compact (FC_TILE)
@@ -169,6 +169,8 @@ def load_library(build_if_missing=True):
     L.rf_amd_diag_lookup_ring.argtypes = [vp]
     L.rf_amd_diag_k4_bitmap_builds.argtypes = []
     L.rf_amd_diag_k4_bitmap_builds.restype = u64
+    L.rf_amd_diag_part16_builds.argtypes = []
+    L.rf_amd_diag_part16_builds.restype = u64
     L.rf_amd_batch_num_filters.argtypes = [vp]
     L.rf_amd_batch_num_filters.restype = u32
     L.rf_amd_filter_add.argtypes = [vp, ctypes.POINTER(RfConfig), ctypes.POINTER(RfImage),
