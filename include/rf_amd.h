@@ -221,13 +221,45 @@ int rf_amd_filter_set_probe_hashes(rf_amd_filter_set *s, const uint32_t *d_hashe
 int rf_amd_filter_set_probe_var_keys(rf_amd_filter_set *s, const uint8_t *d_bytes,
                                      const uint64_t *d_offsets, const uint32_t *d_member,
                                      uint32_t K, uint64_t n, uint64_t *d_found, void *stream);
+/* ragged fan-out probes: per-key member lists of any length, as a trunk path gives them (the
+ * live inflight bundles and the pivot bundle of each node differ from key to key), without
+ * padding to one K. d_member_off holds n + 1 non-decreasing uint64 offsets (unchecked, like the
+ * variable-length keys' offsets); key i is looked up in the members d_member[p] for p in
+ * [d_member_off[i], d_member_off[i+1]), and d_found[p] = routing_filter_lookup's found_values
+ * of that key in that member: the same index p as in d_member. d_member_off[0] need not be 0: a
+ * call over a sub-range of a larger CSR writes into the matching sub-range of a whole d_found,
+ * and nothing outside [d_member_off[0], d_member_off[n]) is written. A key with an empty list
+ * is legal and writes nothing. One key's list holds AT MOST 65,535 ids (a wave's 64 keys then
+ * span fewer than 2^32 pairs); longer lists are not detected. An id >= num_members, a NULL
+ * member and a member whose build failed find nothing (word 0). Everything else is
+ * rf_amd_filter_set_probe_keys': each key is read and hashed once, any key_len > 0 and any
+ * alignment, the seed rule of the keys forms (EINVAL when the non-NULL members' seeds differ;
+ * not for the hashes form), asynchronous on stream (NULL = the engine's), no allocation, no
+ * synchronisation. n == 0 is OK and touches nothing. EINVAL: a NULL set, key_len == 0, with
+ * n > 0 a NULL input, d_member, d_member_off or d_found, and n >= 2^56. There is no all-members
+ * form: that case has one K, and the calls above cover it.
+ * rf_amd_found_compact takes the result as it is: on d_found + d_member_off[0] with m = the
+ * number of pairs (d_member_off[n] - d_member_off[0]); a record's index is then the pair's
+ * position relative to d_member_off[0]. */
+int rf_amd_filter_set_probe_keys_ragged(rf_amd_filter_set *s, const void *d_keys, uint32_t key_len,
+                                        const uint32_t *d_member, const uint64_t *d_member_off,
+                                        uint64_t n, uint64_t *d_found, void *stream);
+int rf_amd_filter_set_probe_var_keys_ragged(rf_amd_filter_set *s, const uint8_t *d_bytes,
+                                            const uint64_t *d_offsets, const uint32_t *d_member,
+                                            const uint64_t *d_member_off, uint64_t n,
+                                            uint64_t *d_found, void *stream);
+int rf_amd_filter_set_probe_hashes_ragged(rf_amd_filter_set *s, const uint32_t *d_hashes,
+                                          const uint32_t *d_member, const uint64_t *d_member_off,
+                                          uint64_t n, uint64_t *d_found, void *stream);
 /* the set bits of m found_values words as an ordered candidate list: record =
  * index << 8 | value, index ascending, and within one word value DESCENDING (the order in
  * which routing_filter_get_next_value hands them out, src/routing_filter.h:94-105; with the
  * fan-out's index = key * K + slot these are trunk_merge_lookup's (key, bundle, branch)
  * candidates, src/trunk.c:6057-6060). *d_count = the total number of candidates (all of them,
  * also when > cap); only the first cap records are written and nothing is written past
- * d_cand[cap) (cap == 0: d_cand may be NULL). Works on the output of any probe call. The same
+ * d_cand[cap) (cap == 0: d_cand may be NULL). Works on the output of any probe call; after a
+ * ragged probe, on d_found + d_member_off[0] with m = the number of pairs, the index being the
+ * pair's position relative to d_member_off[0]. The same
  * input gives the same bytes. Asynchronous on stream (NULL = the engine's), three launches, no
  * allocation: d_scratch (8-byte aligned) holds rf_amd_found_compact_scratch_bytes(m) bytes
  * (callable without a device; non-decreasing in m). m == 0 is OK and sets *d_count = 0.

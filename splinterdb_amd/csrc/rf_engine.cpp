@@ -2088,6 +2088,44 @@ extern "C" int rf_amd_filter_set_probe_hashes(rf_amd_filter_set* s, const uint32
   return set_probe(s, IN_HASH, d_hashes, nullptr, 4, d_member, K, n, d_found, stream);
 }
 
+// the ragged forms: key i against d_member[d_member_off[i] .. d_member_off[i+1])
+static int set_probe_ragged(rf_amd_filter_set* s, int kind, const void* in0, const uint64_t* offs, uint32_t key_len,
+                            const uint32_t* d_member, const uint64_t* d_member_off, uint64_t n, uint64_t* d_found,
+                            void* stream) {
+  if (!s) return fail(RF_AMD_EINVAL, "null filter set");
+  if (kind != IN_HASH && !s->one_seed) return fail(RF_AMD_EINVAL, "keys form over members with different seeds");
+  if (n >= (1ull << 56)) return fail(RF_AMD_EINVAL, "n >= 2^56");
+  if (n == 0) return 0;
+  if (!in0 || !d_member || !d_member_off || !d_found || (kind == IN_VAR && !offs))
+    return fail(RF_AMD_EINVAL, "null probe buffer");
+  HIPCHK(hipSetDevice(s->eng->device));
+  (void)hipGetLastError();
+  int rc = rf_launch_probe_fanout_ragged(stream ? stream : s->eng->stream, kind, in0, offs, key_len, s->seed,
+                                         s->d_groups.as<ProbeGroup>(), s->num_members, d_member, d_member_off, n,
+                                         d_found);
+  if (rc) return fail(RF_AMD_EINVAL, std::string("ragged fan-out probe launch: ") + hipGetErrorString((hipError_t)rc));
+  return 0;
+}
+
+extern "C" int rf_amd_filter_set_probe_keys_ragged(rf_amd_filter_set* s, const void* d_keys, uint32_t key_len,
+                                                   const uint32_t* d_member, const uint64_t* d_member_off, uint64_t n,
+                                                   uint64_t* d_found, void* stream) {
+  if (key_len == 0) return fail(RF_AMD_EINVAL, "key_len 0");
+  return set_probe_ragged(s, fixed_kind(d_keys, key_len), d_keys, nullptr, key_len, d_member, d_member_off, n,
+                          d_found, stream);
+}
+extern "C" int rf_amd_filter_set_probe_var_keys_ragged(rf_amd_filter_set* s, const uint8_t* d_bytes,
+                                                       const uint64_t* d_offsets, const uint32_t* d_member,
+                                                       const uint64_t* d_member_off, uint64_t n, uint64_t* d_found,
+                                                       void* stream) {
+  return set_probe_ragged(s, IN_VAR, d_bytes, d_offsets, 0, d_member, d_member_off, n, d_found, stream);
+}
+extern "C" int rf_amd_filter_set_probe_hashes_ragged(rf_amd_filter_set* s, const uint32_t* d_hashes,
+                                                     const uint32_t* d_member, const uint64_t* d_member_off,
+                                                     uint64_t n, uint64_t* d_found, void* stream) {
+  return set_probe_ragged(s, IN_HASH, d_hashes, nullptr, 4, d_member, d_member_off, n, d_found, stream);
+}
+
 extern "C" int rf_amd_diag_fanout_max_blocks(uint32_t blocks) {
   rf_fanout_set_max_blocks(blocks);
   return 0;

@@ -4376,6 +4376,48 @@ constexpr int FAN_U = RF_FAN_U;  // steps whose loads are in flight together
 #endif
 constexpr uint32_t FAN_VCAP = RF_FAN_VCAP;  // IN_VAR: the key window's bytes (k_probe's and k_hash's size)
 
+// The front half of both fan-out kernels: the hash of key wf + lane of the wave's nk keys (0 past
+// them). sw: the wave's 96 x 16 bytes of key staging (IN_KEYS24), svk: its key window (IN_VAR).
+// Every lane calls it (LDS-DMA, ballots and wave barriers inside).
+template <int KIND>
+__device__ __forceinline__ uint32_t fan_hash_chunk(const void* __restrict__ in0, const uint64_t* __restrict__ offs,
+                                                   uint32_t key_len, uint32_t seed, uint64_t wf, uint32_t nk,
+                                                   uint32_t lane, v4u* sw, uint32_t* svk) {
+  constexpr bool WAVE_KEYS = KIND == IN_KEYS24;
+  constexpr bool WAVE_VAR = KIND == IN_VAR;
+  uint32_t h = 0;
+  if constexpr (WAVE_KEYS) {
+    if (((uintptr_t)in0 & 15) == 0) {
+      const uint8_t* kb = static_cast<const uint8_t*>(in0) + wf * 24;
+      if (nk == WAVE) {
+        keys24_issue_dma(kb, sw, lane);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      } else {
+        keys24_stage_partial(kb, nk * 24, sw, lane);
+      }
+      wave_sync_lds();
+      if (lane < nk) h = keys24_hash_lds(sw, lane, seed);
+    } else if (lane < nk) {
+      h = hash_key<KIND, true>(in0, nullptr, key_len, seed, wf + lane);
+    }
+  } else if constexpr (WAVE_VAR) {
+    // variable-length keys: the wave's 64 keys are one contiguous byte range, staged in a
+    // 4 KiB LDS window and hashed from there (wave_hash_var: ballots and wave barriers, so
+    // every lane calls it). The window state starts empty for every chunk.
+    uint64_t o0 = 0, o1 = 0;
+    if (lane < nk) {
+      o0 = offs[wf + lane];
+      o1 = offs[wf + lane + 1];
+    }
+    uint64_t win0 = 0, win1 = 0;
+    h = wave_hash_var<FAN_VCAP, true>(static_cast<const uint8_t*>(in0), o0, o1, lane < nk, svk, seed, &win0,
+                                      &win1);
+  } else {
+    if (lane < nk) h = hash_key<KIND, true>(in0, nullptr, key_len, seed, wf + lane);
+  }
+  return h;
+}
+
 template <int KIND>
 __global__ __launch_bounds__(FAN_NT) void k_probe_fanout(const void* __restrict__ in0,
                                                          const uint64_t* __restrict__ offs, uint32_t key_len,
@@ -4396,37 +4438,7 @@ __global__ __launch_bounds__(FAN_NT) void k_probe_fanout(const void* __restrict_
   for (uint64_t wc = (uint64_t)blockIdx.x * NW + wv; wc < nwaves; wc += (uint64_t)gridDim.x * NW) {
     const uint64_t wf = wc * WAVE;  // the wave's first key (wave-uniform)
     const uint32_t nk = (uint32_t)min<uint64_t>(WAVE, n - wf);
-    uint32_t h = 0;
-    if constexpr (WAVE_KEYS) {
-      if (((uintptr_t)in0 & 15) == 0) {
-        v4u* sw = s_keys[wv];
-        const uint8_t* kb = static_cast<const uint8_t*>(in0) + wf * 24;
-        if (nk == WAVE) {
-          keys24_issue_dma(kb, sw, lane);
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        } else {
-          keys24_stage_partial(kb, nk * 24, sw, lane);
-        }
-        wave_sync_lds();
-        if (lane < nk) h = keys24_hash_lds(sw, lane, seed);
-      } else if (lane < nk) {
-        h = hash_key<KIND, true>(in0, nullptr, key_len, seed, wf + lane);
-      }
-    } else if constexpr (WAVE_VAR) {
-      // variable-length keys: the wave's 64 keys are one contiguous byte range, staged in a
-      // 4 KiB LDS window and hashed from there (wave_hash_var: ballots and wave barriers, so
-      // every lane calls it). The window state starts empty for every chunk.
-      uint64_t o0 = 0, o1 = 0;
-      if (lane < nk) {
-        o0 = offs[wf + lane];
-        o1 = offs[wf + lane + 1];
-      }
-      uint64_t win0 = 0, win1 = 0;
-      h = wave_hash_var<VCAP, true>(static_cast<const uint8_t*>(in0), o0, o1, lane < nk, s_vk[wv], seed, &win0,
-                                    &win1);
-    } else {
-      if (lane < nk) h = hash_key<KIND, true>(in0, nullptr, key_len, seed, wf + lane);
-    }
+    const uint32_t h = fan_hash_chunk<KIND>(in0, offs, key_len, seed, wf, nk, lane, s_keys[wv], s_vk[wv]);
     s_h[wv][lane] = h;
     wave_sync_lds();
     const uint64_t pbase = wf * K;          // the wave's first pair (n K < 2^56)
@@ -4499,6 +4511,123 @@ __global__ __launch_bounds__(FAN_NT) void k_probe_fanout(const void* __restrict_
       }
     }
     wave_sync_lds();  // the next chunk's keys, key window and hashes overwrite this one's
+  }
+}
+
+// ---- multi-get: ragged fan-out, per-key member lists of any length ----------------------
+// Key i is looked up in the members member[moff[i] .. moff[i+1]) (rf_amd_filter_set_probe_*_ragged:
+// n + 1 non-decreasing pair offsets, moff[0] any value); found[p] answers member[p]. The front
+// half is k_probe_fanout's (fan_hash_chunk, hashes parked in LDS). The wave then parks its 65
+// offsets in LDS relative to its first pair (a list holds at most 65,535 ids: 32 bits) and
+// walks its pairs 64 per step: lane p of a step reads member[base + p] and stores
+// found[base + p], coalesced, and finds its key -- the last k with off[k] <= p, so that empty
+// lists own no pair -- by a 6-step search of the parked offsets, which carries nothing from one
+// step or chunk to the next. The entries of the keys past a partial wave's nk hold the wave's
+// pair count, so the search never names them. From the member id on the path is
+// k_probe_fanout's. A wave whose keys own no pairs reads its two end offsets and nothing else.
+template <int KIND>
+__global__ __launch_bounds__(FAN_NT) void k_probe_fanout_ragged(const void* __restrict__ in0,
+                                                                const uint64_t* __restrict__ offs,
+                                                                uint32_t key_len, uint32_t seed,
+                                                                const ProbeGroup* __restrict__ groups, uint32_t ng,
+                                                                const uint32_t* __restrict__ member,
+                                                                const uint64_t* __restrict__ moff, uint64_t n,
+                                                                uint64_t* __restrict__ found) {
+  constexpr bool WAVE_KEYS = KIND == IN_KEYS24;
+  constexpr bool WAVE_VAR = KIND == IN_VAR;
+  constexpr int NW = FAN_NT / WAVE;
+  __shared__ v4u s_keys[NW][WAVE_KEYS ? 96 : 1];
+  __shared__ __attribute__((aligned(16))) uint32_t s_vk[WAVE_VAR ? NW : 1][WAVE_VAR ? FAN_VCAP / 4 + 4 : 1];
+  __shared__ uint32_t s_h[NW][WAVE];
+  __shared__ uint32_t s_off[NW][WAVE];  // off[k] - off[0] of the wave's keys; np past nk
+  const uint32_t lane = threadIdx.x & (WAVE - 1);
+  const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x) / WAVE;
+  const uint64_t nwaves = (n + WAVE - 1) / WAVE;
+  for (uint64_t wc = (uint64_t)blockIdx.x * NW + wv; wc < nwaves; wc += (uint64_t)gridDim.x * NW) {
+    const uint64_t wf = wc * WAVE;  // the wave's first key (wave-uniform)
+    const uint32_t nk = (uint32_t)min<uint64_t>(WAVE, n - wf);
+    const uint64_t pbase = moff[wf];                   // the wave's first pair
+    const uint32_t np = (uint32_t)(moff[wf + nk] - pbase);  // its pairs (<= 64 * 65,535)
+    if (np == 0) continue;  // nothing of this chunk is in LDS: no sync owed
+    s_off[wv][lane] = lane < nk ? (uint32_t)(moff[wf + lane] - pbase) : np;
+    const uint32_t h = fan_hash_chunk<KIND>(in0, offs, key_len, seed, wf, nk, lane, s_keys[wv], s_vk[wv]);
+    s_h[wv][lane] = h;
+    wave_sync_lds();
+    for (uint32_t p0 = lane; p0 < np + lane; p0 += (uint32_t)WAVE * FAN_U) {  // p0 - lane: wave-uniform
+      uint32_t g[FAN_U], st[FAN_U], px[FAN_U], pf[FAN_U], hh[FAN_U], pj[FAN_U], pr[FAN_U];
+      v4u Q[FAN_U][4];
+      // member ids: one coalesced read per step
+#pragma unroll
+      for (int u = 0; u < FAN_U; u++) {
+        const uint32_t p = p0 + (uint32_t)u * WAVE;
+        g[u] = 0xffffffffu;
+        if (p < np) g[u] = __builtin_nontemporal_load(member + pbase + p);
+      }
+      // the pair's key: the last k with off[k] <= p (off[0] = 0 <= p); p >= np finds a key below
+      // 64 whose hash nothing uses
+#pragma unroll
+      for (int u = 0; u < FAN_U; u++) {
+        const uint32_t p = p0 + (uint32_t)u * WAVE;
+        uint32_t k = 0;
+#pragma unroll
+        for (uint32_t w = WAVE / 2; w >= 1; w >>= 1)
+          if (s_off[wv][k + w] <= p) k += w;
+        hh[u] = s_h[wv][k];
+      }
+      // group heads: scalar loads through the constant address space when the whole wave names
+      // one member, one plain load per lane otherwise
+      uint64_t pl[FAN_U];
+#pragma unroll
+      for (int u = 0; u < FAN_U; u++) {
+        if (g[u] >= ng) g[u] = 0xffffffffu;  // NULL_ROUTING_FILTER by position: finds nothing
+        const uint32_t gs = __builtin_amdgcn_readfirstlane(g[u]);
+        uint32_t err = 1;
+        px[u] = pf[u] = 0;
+        pl[u] = 0;
+        if (__builtin_amdgcn_ballot_w64(g[u] != gs) == 0) {
+          if (gs != 0xffffffffu) {
+            const ProbeGroup* G = groups + gs;
+            px[u] = sload32(&G->x);
+            err = sload32(&G->err);
+            pf[u] = sload32(&G->fpl);
+            pl[u] = sload64(&G->lines);
+          }
+        } else if (g[u] != 0xffffffffu) {
+          const ProbeGroup* G = groups + g[u];
+          px[u] = G->x;
+          err = G->err;
+          pf[u] = G->fpl;
+          pl[u] = (uint64_t)(uintptr_t)G->lines;
+        }
+        st[u] = err ? 0u : ((px[u] >> 24) ? 1u : 2u);  // 0 nothing found, 1 probe line, 2 no lines: walk
+      }
+      // probe lines (probe_line's addressing)
+#pragma unroll
+      for (int u = 0; u < FAN_U; u++) {
+        pj[u] = pr[u] = 0;
+        if (st[u] == 1) {
+          const uint32_t rem = (px[u] >> 8) & 0xff, lgl = px[u] >> 24, fp_size = pf[u] & 0xff;
+          uint32_t bucket, remainder;
+          split_fp(hh[u], fp_size, rem, bucket, remainder);
+          pr[u] = remainder;
+          pj[u] = bucket & ((1u << (lgl - 1)) - 1);
+          const v4u* lp = reinterpret_cast<const v4u*>((uintptr_t)pl[u]) + (uint64_t)(bucket >> (lgl - 1)) * 4;
+#pragma unroll
+          for (int k = 0; k < 4; k++) Q[u][k] = lp[k];
+        }
+      }
+      // decode and store
+#pragma unroll
+      for (int u = 0; u < FAN_U; u++) {
+        const uint32_t p = p0 + (uint32_t)u * WAVE;
+        uint64_t r = 0;
+        bool walk = st[u] == 2;
+        if (st[u] == 1) walk = !line_decode(Q[u], pj[u], pr[u], px[u] & 0xff, (px[u] >> 16) & 0xff, r);
+        if (walk) r = probe_group(groups[g[u]], hh[u]);
+        if (p < np) __builtin_nontemporal_store(r, found + pbase + p);
+      }
+    }
+    wave_sync_lds();  // the next chunk's keys, key window, hashes and offsets overwrite this one's
   }
 }
 
@@ -4613,6 +4742,28 @@ extern "C" int rf_launch_probe_fanout(void* stream, int kind, const void* in0, c
   if (cap && nblk > cap) nblk = cap;
   const dim3 g((uint32_t)nblk), b(FAN_NT);
 #define L(KD) hipLaunchKernelGGL((k_probe_fanout<KD>), g, b, 0, (hipStream_t)stream, in0, offs, key_len, seed, groups, ng, member, K, n, found)
+  switch (kind) {
+    KEY_KIND_CASES(L)
+    case IN_HASH: L(IN_HASH); break;
+    default: return (int)hipErrorInvalidValue;
+  }
+#undef L
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : (int)e;
+}
+
+// the ragged form: moff = the n + 1 pair offsets of the keys' member lists
+extern "C" int rf_launch_probe_fanout_ragged(void* stream, int kind, const void* in0, const uint64_t* offs,
+                                             uint32_t key_len, uint32_t seed, const ProbeGroup* groups, uint32_t ng,
+                                             const uint32_t* member, const uint64_t* moff, uint64_t n,
+                                             uint64_t* found) {
+  if (n == 0) return 0;
+  uint64_t nblk = ((n + WAVE - 1) / WAVE + FAN_NT / WAVE - 1) / (FAN_NT / WAVE);
+  if (nblk > 0x7fffffffull) nblk = 0x7fffffffull;
+  const uint32_t cap = g_fanout_max_blocks.load(std::memory_order_relaxed);
+  if (cap && nblk > cap) nblk = cap;
+  const dim3 g((uint32_t)nblk), b(FAN_NT);
+#define L(KD) hipLaunchKernelGGL((k_probe_fanout_ragged<KD>), g, b, 0, (hipStream_t)stream, in0, offs, key_len, seed, groups, ng, member, moff, n, found)
   switch (kind) {
     KEY_KIND_CASES(L)
     case IN_HASH: L(IN_HASH); break;

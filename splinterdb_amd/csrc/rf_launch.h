@@ -57,7 +57,11 @@ int rf_launch_lookup_server(void* stream, const rf::SrvReq* ring, rf::SrvRes* re
 int rf_launch_probe_fanout(void* stream, int kind, const void* in0, const uint64_t* offs, uint32_t key_len,
                            uint32_t seed, const rf::ProbeGroup* groups, uint32_t ng, const uint32_t* member,
                            uint32_t K, uint64_t n, uint64_t* found);
-// diagnostics (rf_amd_diag_fanout_max_blocks): a cap on the fan-out grid; 0 = none
+// the ragged form: key i against member[moff[i] .. moff[i+1]) (n + 1 pair offsets), found[p] for member[p]
+int rf_launch_probe_fanout_ragged(void* stream, int kind, const void* in0, const uint64_t* offs, uint32_t key_len,
+                                  uint32_t seed, const rf::ProbeGroup* groups, uint32_t ng, const uint32_t* member,
+                                  const uint64_t* moff, uint64_t n, uint64_t* found);
+// diagnostics (rf_amd_diag_fanout_max_blocks): a cap on both fan-out grids; 0 = none
 void rf_fanout_set_max_blocks(uint32_t blocks);
 uint64_t rf_found_compact_tiles(uint64_t m);
 // scratch: ntiles 64-bit offsets, then ntiles 32-bit sums

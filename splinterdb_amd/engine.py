@@ -62,6 +62,8 @@ EXPORTED = [
     "rf_amd_found_compact_scratch_bytes", "rf_amd_found_compact",
     "rf_amd_filter_set_probe_var_keys", "rf_amd_batch_probe_var_keys_runs", "rf_amd_filter_lookup_var_keys",
     "rf_amd_diag_fanout_max_blocks", "rf_amd_diag_lookup_paths", "rf_amd_diag_part16_builds",
+    "rf_amd_filter_set_probe_keys_ragged", "rf_amd_filter_set_probe_var_keys_ragged",
+    "rf_amd_filter_set_probe_hashes_ragged",
 ]
 ROUTE_MAX_WORLD = 16
 FOUND_COMPACT_TILE = 4096  # found words per workgroup of rf_amd_found_compact (FC_TILE)
@@ -246,6 +248,9 @@ def load_library(build_if_missing=True):
     L.rf_amd_batch_probe_var_keys_runs.argtypes = [vp, vp, vp, ctypes.POINTER(u64), vp, vp]
     L.rf_amd_filter_lookup_var_keys.argtypes = [vp, ctypes.POINTER(RfConfig), ctypes.POINTER(RfImage),
                                                 vp, vp, u64, vp]
+    L.rf_amd_filter_set_probe_keys_ragged.argtypes = [vp, vp, u32, vp, vp, u64, vp, vp]
+    L.rf_amd_filter_set_probe_var_keys_ragged.argtypes = [vp, vp, vp, vp, vp, u64, vp, vp]
+    L.rf_amd_filter_set_probe_hashes_ragged.argtypes = [vp, vp, vp, vp, u64, vp, vp]
     L.rf_amd_diag_fanout_max_blocks.argtypes = [u32]
     L.rf_amd_host_alloc.argtypes = [vp, u64, ctypes.POINTER(vp)]
     L.rf_amd_host_free.argtypes = [vp, vp]
@@ -918,6 +923,16 @@ def found_candidates(found: np.ndarray) -> np.ndarray:
     return (nz[row].astype(np.uint64) << np.uint64(8)) | (np.uint64(63) - col.astype(np.uint64))
 
 
+def ragged_pair_keys(offsets, pair_index) -> np.ndarray:
+    """Host mirror of the ragged multi-get's record-to-key step: the key that owns each pair,
+    pair_index being relative to offsets[0] as rf_amd_found_compact's record indices are after
+    a ragged probe (record >> 8). offsets: the n + 1 non-decreasing pair offsets; the key of
+    pair p is the last k with offsets[k] <= p, so empty lists own nothing."""
+    off = np.ascontiguousarray(offsets).reshape(-1).view(np.uint64).astype(np.int64)
+    p = np.asarray(pair_index).astype(np.int64) + off[0]
+    return np.searchsorted(off, p, side="right").astype(np.int64) - 1
+
+
 def found_compact_scratch_bytes(m) -> int:
     return int(load_library().rf_amd_found_compact_scratch_bytes(m))
 
@@ -1011,6 +1026,55 @@ class FilterSet:
         d_found = torch.empty(n * K, dtype=torch.int64, device=d_offsets.device)
         self.probe_var_keys(d_bytes, d_offsets, d_member, K, n, d_found, stream)
         return self._compact_found(d_found, n, K, cap, stream)
+
+    def probe_keys_ragged(self, d_keys, key_len, d_member, d_member_off, n, d_found, stream=None):
+        """key i in members d_member[d_member_off[i] : d_member_off[i+1]] (n + 1 uint64 pair
+        offsets, at most 65,535 ids per key) into d_found at the same positions; each key is
+        read and hashed once, and nothing outside the offsets' range is written"""
+        _check(load_library().rf_amd_filter_set_probe_keys_ragged(self.h, _dptr(d_keys), key_len, _dptr(d_member),
+                                                                  _dptr(d_member_off), n, _dptr(d_found),
+                                                                  _stream(stream)))
+
+    def probe_var_keys_ragged(self, d_bytes, d_offsets, d_member, d_member_off, n, d_found, stream=None):
+        """probe_keys_ragged for variable-length keys (d_offsets: n + 1 uint64 byte offsets)"""
+        _check(load_library().rf_amd_filter_set_probe_var_keys_ragged(self.h, _dptr(d_bytes), _dptr(d_offsets),
+                                                                      _dptr(d_member), _dptr(d_member_off), n,
+                                                                      _dptr(d_found), _stream(stream)))
+
+    def probe_hashes_ragged(self, d_hashes, d_member, d_member_off, n, d_found, stream=None):
+        _check(load_library().rf_amd_filter_set_probe_hashes_ragged(self.h, _dptr(d_hashes), _dptr(d_member),
+                                                                    _dptr(d_member_off), n, _dptr(d_found),
+                                                                    _stream(stream)))
+
+    def multiget_ragged(self, d_keys, key_len, d_member, d_member_off, n, cap=None, stream=None):
+        """probe_keys_ragged + found_compact over the pairs: returns (d_cand, count, d_key). The
+        first `count` records of d_cand are the candidates pair << 8 | value in order, pair
+        being relative to d_member_off[0]; d_key[j] is the key of record j. The pair count is
+        read from the offsets once; then as multiget."""
+        return self._multiget_ragged(d_member_off, n, cap, stream,
+                                     lambda d_found: self.probe_keys_ragged(d_keys, key_len, d_member, d_member_off,
+                                                                            n, d_found, stream))
+
+    def multiget_var_ragged(self, d_bytes, d_offsets, d_member, d_member_off, n, cap=None, stream=None):
+        """multiget_ragged for variable-length keys (probe_var_keys_ragged + found_compact)"""
+        return self._multiget_ragged(d_member_off, n, cap, stream,
+                                     lambda d_found: self.probe_var_keys_ragged(d_bytes, d_offsets, d_member,
+                                                                                d_member_off, n, d_found, stream))
+
+    def _multiget_ragged(self, d_member_off, n, cap, stream, probe):
+        import torch
+        dev = d_member_off.device
+        first, last = (int(x) for x in d_member_off[[0, n]].tolist()) if n else (0, 0)  # the one read
+        m = last - first
+        # the m words of the pairs alone: the probe indexes from d_member_off[0] and writes
+        # nothing below it, so it takes the address that word 0 would have
+        d_found = torch.empty(m, dtype=torch.int64, device=dev)
+        if m:
+            probe(d_found.data_ptr() - 8 * first)
+        d_cand, count = self._compact_found(d_found, m, 1, max(1, n) if cap is None else cap, stream)
+        d_key = torch.searchsorted(d_member_off[:n + 1].view(torch.int64), (d_cand[:count] >> 8) + first,
+                                   right=True) - 1
+        return d_cand, count, d_key
 
     def _compact_found(self, d_found, n, K, cap, stream):
         """the multi-get's tail: the candidates of d_found[:n * K] as (d_cand, count)"""

@@ -18,7 +18,16 @@ probe_hashes. Key i is a member of filter i % 64: each filter is built (build_ha
 hashes of its n / 64 probe keys and random hashes up to its 2^20. Default output:
 profiles/multiget_var.json.
 
-    timeout -k 10 600 python tools/multiget.py [--var] [--filters 64] [--keys 1048576]
+--ragged: per-key member lists of different lengths on the same filters and keys (with --var:
+variable-length keys). Key i has min(16, 1 + Geometric(1/3)) random members (seeded, mean about
+4). Timed with the same method: (a) the ragged probe (FilterSet.probe_keys_ragged) and the
+compaction of its pairs, against (b) the same lists padded to K = 16 with the id num_members
+through the fixed form (probe_keys) and the compaction of its n * 16 words; and (c) uniform
+K = 4 lists through both kernels. The non-padded words of (a) and (b), and both outputs of (c),
+are compared before anything is timed. Default output: profiles/multiget_ragged.json
+(profiles/multiget_var_ragged.json).
+
+    timeout -k 10 600 python tools/multiget.py [--var] [--ragged] [--filters 64] [--keys 1048576]
                                                [--n 16777216] [--k 4] [--rounds 7] [--warmup 2]
                                                [--out profiles/multiget.json]
 """
@@ -37,6 +46,119 @@ from splinterdb_amd import engine as E  # noqa: E402
 from splinterdb_amd import keys as K  # noqa: E402
 
 
+KPAD = 16  # --ragged: the longest list, and the K that the padded form needs
+
+
+def ragged(args, fset, eng, stream, kin, own, mean_len, timed, rng):
+    """--ragged: (a) ragged probe + compaction against (b) the lists padded to KPAD through the
+    fixed form + compaction, and (c) uniform K = 4 through both kernels; kin: the keys'
+    arguments, own[i]: the filter that holds key i"""
+    import numpy as np
+    F, n = args.filters, args.n
+    dev, st = own.device, stream.cuda_stream
+    probe_r = fset.probe_var_keys_ragged if args.var else fset.probe_keys_ragged
+    probe_f = fset.probe_var_keys if args.var else fset.probe_keys
+    counts = np.minimum(KPAD, 1 + np.random.default_rng(7).geometric(1.0 / 3.0, size=n)).astype(np.int64)
+    off_h = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(counts, out=off_h[1:])
+    m = int(off_h[-1])
+    with torch.cuda.stream(stream):
+        g = torch.Generator(device=dev)
+        g.manual_seed(8)
+        off = torch.from_numpy(off_h).to(dev)
+        d_counts = torch.from_numpy(counts).to(dev)
+        key = torch.repeat_interleave(torch.arange(n, device=dev), d_counts)       # the pair's key
+        at = key * KPAD + (torch.arange(m, device=dev) - off[key])                  # its place in the padded form
+        member_r = torch.randint(0, F, (m,), device=dev, generator=g).to(torch.int32)
+        member_p = torch.full((n * KPAD,), F, dtype=torch.int32, device=dev)       # id num_members: finds nothing
+        member_p[at] = member_r
+        member_u = torch.randint(0, F, (n * 4,), device=dev, generator=g).to(torch.int32)
+        off_u = torch.arange(n + 1, device=dev, dtype=torch.int64) * 4
+        found_r = torch.zeros(m, dtype=torch.int64, device=dev)
+        found_p = torch.zeros(n * KPAD, dtype=torch.int64, device=dev)
+        found_ur = torch.zeros(n * 4, dtype=torch.int64, device=dev)
+        found_uf = torch.zeros(n * 4, dtype=torch.int64, device=dev)
+        d_count = torch.zeros(1, dtype=torch.int64, device=dev)
+        # every output once, compared before anything is timed
+        probe_r(*kin, member_r, off, n, found_r, stream=st)
+        probe_f(*kin, member_p, KPAD, n, found_p, stream=st)
+        probe_r(*kin, member_u, off_u, n, found_ur, stream=st)
+        probe_f(*kin, member_u, 4, n, found_uf, stream=st)
+    stream.synchronize()
+    with torch.cuda.stream(stream):
+        assert torch.equal(found_r, found_p[at]), "ragged and padded words disagree"
+        assert int(torch.count_nonzero(found_p)) == int(torch.count_nonzero(found_r)), "a padded slot found something"
+        assert torch.equal(found_ur, found_uf), "uniform K = 4: the two kernels disagree"
+        mine = member_r.to(torch.int64) == own[key]
+        hits = int(((found_r >> member_r.to(torch.int64)) & 1)[mine].sum())
+        assert hits == int(mine.sum()) and hits > 0, "false negative"
+        del mine, key, at
+        E.found_compact(found_r, m, None, d_count, stream=st, engine=eng)
+    stream.synchronize()
+    count = int(d_count.item())
+    with torch.cuda.stream(stream):
+        E.found_compact(found_p, n * KPAD, None, d_count, stream=st, engine=eng)
+    stream.synchronize()
+    assert int(d_count.item()) == count, "the padded form's candidates differ in number"
+    with torch.cuda.stream(stream):
+        d_cand = torch.zeros(max(count, 1), dtype=torch.int64, device=dev)
+    stream.synchronize()
+
+    ways = {
+        "ragged_probe": lambda: probe_r(*kin, member_r, off, n, found_r, stream=st),
+        "padded_probe": lambda: probe_f(*kin, member_p, KPAD, n, found_p, stream=st),
+        "ragged_compact": lambda: E.found_compact(found_r, m, d_cand, d_count, stream=st, engine=eng),
+        "padded_compact": lambda: E.found_compact(found_p, n * KPAD, d_cand, d_count, stream=st, engine=eng),
+        "uniform4_ragged_probe": lambda: probe_r(*kin, member_u, off_u, n, found_ur, stream=st),
+        "uniform4_fixed_probe": lambda: probe_f(*kin, member_u, 4, n, found_uf, stream=st),
+    }
+    t = {w: [] for w in ways}
+    for r in range(args.warmup + args.rounds):
+        for w, fn in ways.items():  # alternating: one of each per round
+            ms = timed(fn)
+            if r >= args.warmup:
+                t[w].append(ms)
+    assert int(d_count.item()) == count
+    t["ragged_total"] = [a + b for a, b in zip(t["ragged_probe"], t["ragged_compact"])]
+    t["padded_total"] = [a + b for a, b in zip(t["padded_probe"], t["padded_compact"])]
+
+    def versus(a, b):
+        return {"ranges_touch": not (max(a) < min(b) or max(b) < min(a)),
+                "ragged_faster_beyond_ranges": bool(max(a) < min(b)),
+                "ragged_slower_beyond_ranges": bool(max(b) < min(a))}
+
+    mean_list = m / n
+    key_bytes = round(mean_len + 8, 3) if args.var else 24
+    out = {
+        "what": ("ragged multi-get of n %s, key i against min(16, 1 + Geometric(1/3)) random members of one "
+                 "batch of F filters: (a) FilterSet.probe_%skeys_ragged + found_compact of the pairs against (b) the "
+                 "same lists padded to K = 16 with id num_members through probe_%skeys + found_compact of the n * 16 "
+                 "words, and (c) uniform K = 4 lists through both kernels; alternating rounds in one process, HIP "
+                 "events on the launch stream" % (("variable-length keys (keys.var_keys, 8-100 B)", "var_", "var_")
+                                                  if args.var else ("24-byte keys", "", ""))),
+        "config": {"filters": F, "keys_per_filter": args.keys, "n": n, "pairs": m, "mean_list": round(mean_list, 4),
+                   "max_list": int(counts.max()), "K_padded": KPAD, "rounds": args.rounds, "warmup": args.warmup,
+                   "fingerprint_size": 26, "log_index_size": 8},
+        "ms": {w: rng(v) for w, v in t.items()},
+        "probe": versus(t["ragged_probe"], t["padded_probe"]),
+        "compact": versus(t["ragged_compact"], t["padded_compact"]),
+        "probe_plus_compact": versus(t["ragged_total"], t["padded_total"]),
+        "uniform4_probe": versus(t["uniform4_ragged_probe"], t["uniform4_fixed_probe"]),
+        # per pair an id, a line and a word, and the pair's share of its key (--var: mean length + 8 of offset)
+        # and of the key's 8-byte list offset
+        "ragged_algorithmic_bytes_per_pair": round(4 + 64 + 8 + (key_bytes + 8) / mean_list, 3),
+        "candidates": count,
+        "ragged_found_bytes": m * 8,
+        "padded_found_bytes": n * KPAD * 8,
+        "verified": "the non-padded words of (a) and (b) equal, no padded slot found anything, both outputs of (c) "
+                    "equal; every (key, own filter) pair found",
+        "device": torch.cuda.get_device_name(0),
+    }
+    if args.var:
+        out["config"]["mean_key_len"] = round(mean_len, 3)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--filters", type=int, default=64)
@@ -46,10 +168,12 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--var", action="store_true", help="variable-length keys (8-100 B)")
+    ap.add_argument("--ragged", action="store_true", help="per-key member lists: ragged against padded to K = 16")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "multiget_var.json" if args.var else "multiget.json")
+        name = "multiget" + ("_var" if args.var else "") + ("_ragged" if args.ragged else "") + ".json"
+        args.out = os.path.join(ROOT, "profiles", name)
     if not torch.cuda.is_available():
         sys.exit("multiget.py measures on the GPU: no HIP device")
     F, nk, n, Kf = args.filters, args.keys, args.n, args.k
@@ -122,6 +246,23 @@ def main():
         stream.synchronize()
         return a.elapsed_time(b)
 
+    def rng(v):
+        return {"min": round(min(v), 4), "max": round(max(v), 4), "rounds": [round(x, 4) for x in v]}
+
+    if args.ragged:
+        del found_a, found_b, member
+        kin = (d_bytes, d_offs) if args.var else (keys, 24)
+        out = ragged(args, fset, eng, stream, kin, own, mean_len, timed, rng)
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            json.dump(out, fh, indent=1)
+            fh.write("\n")
+        print(json.dumps(out))
+        fset.close()
+        batch.close()
+        eng.close()
+        return
+
     t = {"fanout": [], "replicate": []}
     for r in range(args.warmup + args.rounds):
         for way, fn in (("fanout", fanout), ("replicate", replicate)):
@@ -156,9 +297,6 @@ def main():
         if r >= args.warmup:
             t_dense.append(a)
             t_cand.append(b)
-
-    def rng(v):
-        return {"min": round(min(v), 4), "max": round(max(v), 4), "rounds": [round(x, 4) for x in v]}
 
     fa, rb = t["fanout"], t["replicate"]
     what = ("multi-get of n 24-byte keys, K random members per key, one batch of F filters: "
