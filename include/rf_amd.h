@@ -196,6 +196,51 @@ int  rf_amd_filter_set_create(rf_amd_engine *e, rf_amd_batch *const *batches,
                               rf_amd_filter_set **out);
 void rf_amd_filter_set_destroy(rf_amd_filter_set *s);
 uint32_t rf_amd_filter_set_num_members(const rf_amd_filter_set *s);
+/* Sets that follow compactions (each maplet compaction replaces one bundle's filter,
+ * maplet_compaction_task, src/trunk.c:3815-3868): a set with room to grow, members replaced in
+ * stream order, and a stream-ordered destroy, so a resident set lives across compactions without
+ * a host wait. The intended sequence, all on one stream: build the new batch,
+ * rf_amd_filter_set_update, rf_amd_batch_destroy_on the old batch.
+ * create_cap is rf_amd_filter_set_create with room for `capacity` members (EINVAL: capacity <
+ * num_members, capacity == 0): members [num_members, capacity) start as NULL_ROUTING_FILTER.
+ * rf_amd_filter_set_create makes capacity = num_members.
+ * update: member member_id[i] becomes filter filter_index[i] (NULL: 0) of batches[i] (NULL batch:
+ * NULL_ROUTING_FILTER, which is how a member is cleared), for i < count. Asynchronous on stream
+ * (NULL = the engine's): a probe queued there before the call sees the old members, one queued
+ * after it the new ones; the caller orders probes on other streams, as for any device-pointer
+ * call. The call waits for nothing -- the new members' builds included -- and allocates nothing
+ * on the device (nor on the host, while count <= capacity). Calls on one set -- updates, and
+ * updates against probes -- are serialised by the caller: the set keeps the call's host scratch.
+ * A member's batch must be built in the sense of the other calls (its build has been issued);
+ * the caller orders that build before the update, on the same stream or with an event. The
+ * member's build error is read on the device, in stream order, so a member whose build is
+ * rejected finds nothing without the host ever having read its bits (bits the host knows
+ * already, e.g. of an imported batch, travel with the call). rf_amd_batch_trim keeps what the
+ * update reads: a trimmed batch may become a member.
+ * Ids lie in [0, capacity); num_members becomes max(num_members, largest id + 1) when the call
+ * returns, and later probes use it. Slots never set are NULL members, so a gap finds nothing. A
+ * set does not shrink and does not grow beyond its capacity (that takes a new set). An id named
+ * twice in one call: the last entry wins. The seed rule of the keys forms follows the membership
+ * after the update: putting back a member with the common seed makes them legal again.
+ * EINVAL, and then nothing has changed -- neither a member nor num_members nor the seed rule: a
+ * NULL set; with count > 0 a NULL member_id or batches; an id >= capacity; a batch that is
+ * unbuilt or of another engine; a filter index out of range. Every entry is checked before the
+ * first is applied. count == 0 is OK and touches nothing. The one exception: a launch that the
+ * HIP runtime itself refuses (a faulted stream; the HIP error is in rf_amd_last_error) also
+ * returns EINVAL, after the host state has changed and possibly some of the launches have gone
+ * out; the set's members are then undefined and the set is good only for destroy.
+ * The set still holds addresses and no references: a replaced batch must outlive the last probe
+ * ordered before the update.
+ * destroy_on is the stream-ordered destroy, as rf_amd_batch_destroy_on: the caller has ordered
+ * every use of s before the current end of `stream`; does not wait. */
+int rf_amd_filter_set_create_cap(rf_amd_engine *e, rf_amd_batch *const *batches,
+                                 const uint32_t *filter_index, uint32_t num_members,
+                                 uint32_t capacity, rf_amd_filter_set **out);
+uint32_t rf_amd_filter_set_capacity(const rf_amd_filter_set *s);
+int rf_amd_filter_set_update(rf_amd_filter_set *s, const uint32_t *member_id,
+                             rf_amd_batch *const *batches, const uint32_t *filter_index,
+                             uint32_t count, void *stream);
+int rf_amd_filter_set_destroy_on(rf_amd_filter_set *s, void *stream);
 /* fan-out probes: key i is looked up in the K members d_member[i*K .. i*K+K) (row-major; an
  * id >= num_members finds nothing). d_member == NULL: K must equal num_members and slot j is
  * member j. d_found[i*K + j] = routing_filter_lookup's found_values of key i in that member.

@@ -26,6 +26,7 @@
 #include "../../include/rf_amd_diag.h"
 #include "rf_plan.h"
 #include "rf_batch_plan.h"
+#include "rf_set_plan.h"
 #include "rf_launch.h"
 
 using namespace rf;
@@ -1243,11 +1244,12 @@ static int batch_errors(rf_amd_batch* b) {
   return 0;
 }
 
-static ProbeGroup probe_group_of(const rf_amd_batch* b, uint32_t f) {
+// filter f's entry of a group table, with the error bits `err`
+static ProbeGroup probe_group_with(const rf_amd_batch* b, uint32_t f, uint32_t err) {
   const FilterPlan& p = b->plans[f];
   ProbeGroup g;
   g.x = pplan_word(p);
-  g.err = b->err_host[f];
+  g.err = err;
   g.fpl = b->cfg.fingerprint_size | (b->cfg.log_index_size << 8);
   g.pad = 0;
   g.lines = b->d_lines.as<uint4>() + 4ull * p.line_base;
@@ -1255,6 +1257,8 @@ static ProbeGroup probe_group_of(const rf_amd_batch* b, uint32_t f) {
   g.slots = b->d_slots.as<uint64_t>() + p.idx_base;
   return g;
 }
+// the same with the build's own bits (after batch_errors)
+static ProbeGroup probe_group_of(const rf_amd_batch* b, uint32_t f) { return probe_group_with(b, f, b->err_host[f]); }
 
 // Probe modes of a round trip: inputs read by the kernel from pinned host memory (small
 // calls: no copy command) or copied to the device with one H2D first; results always written
@@ -1998,49 +2002,148 @@ extern "C" int rf_amd_probe_many_hashes_host(rf_amd_engine* e, rf_amd_batch* con
 // g's probe lines, pages and slots by address. Those buffers stay where they are for the
 // batch's lifetime -- rf_amd_batch_trim keeps d_lines, d_pages and d_slots and releases only the
 // others -- so a set outlives a trim of its members without re-resolving anything.
-struct rf_amd_filter_set {
+// The table has `capacity` entries, num_members of them in use (the probes' bound); the others
+// are NULL members. A set is its host state (rf_set_plan.h: the count, each slot's seed and
+// whether a filter sits in it, the seed rule of the keys forms) plus that table.
+struct rf_amd_filter_set : SetState {
   rf_amd_engine* eng = nullptr;
-  uint32_t num_members = 0;
-  uint32_t seed = 0;       // of every non-NULL member, when they agree
-  bool one_seed = true;
   DevBuf d_groups;
+  // what a member update hands the planner and gets back, kept between calls
+  std::vector<uint32_t> upd_seed;
+  std::vector<uint8_t> upd_null;
+  SetUpdatePlan upd_plan;
 };
 
-extern "C" int rf_amd_filter_set_create(rf_amd_engine* e, rf_amd_batch* const* batches, const uint32_t* filter_index,
-                                        uint32_t num_members, rf_amd_filter_set** out) {
+static ProbeGroup null_group() {  // NULL_ROUTING_FILTER: finds nothing
+  ProbeGroup g;
+  memset(&g, 0, sizeof(g));
+  g.err = 1;
+  return g;
+}
+
+// a member named by a call: nullptr batch = NULL_ROUTING_FILTER, else a built batch of engine e
+// and one of its filters
+static int check_member(const rf_amd_engine* e, const rf_amd_batch* b, uint32_t f) {
+  if (!b) return 0;
+  if (!b->built || b->eng != e) return fail(RF_AMD_EINVAL, "member on an unbuilt or foreign batch");
+  if (f >= b->F) return fail(RF_AMD_EINVAL, "bad filter index");
+  return 0;
+}
+
+static int filter_set_create(rf_amd_engine* e, rf_amd_batch* const* batches, const uint32_t* filter_index,
+                             uint32_t num_members, uint32_t capacity, rf_amd_filter_set** out) {
   if (!e) return fail(RF_AMD_ENODEV, "no engine");
   if (!out) return fail(RF_AMD_EINVAL, "null out-param");
   *out = nullptr;
   if (num_members && !batches) return fail(RF_AMD_EINVAL, "null member arrays");
+  if (capacity < num_members) return fail(RF_AMD_EINVAL, "capacity below num_members");
   HIPCHK(hipSetDevice(e->device));
   auto s = std::make_unique<rf_amd_filter_set>();
   s->eng = e;
-  s->num_members = num_members;
-  std::vector<ProbeGroup> groups(num_members);
-  bool any = false;
+  s->init(capacity);
+  std::vector<ProbeGroup> groups(capacity, null_group());
+  std::vector<uint32_t> ids(num_members);
+  // room for any later call of up to `capacity` entries: an update then allocates nothing on
+  // the host either
+  s->upd_seed.reserve(capacity);
+  s->upd_null.reserve(capacity);
+  s->upd_plan.order.reserve(capacity);
+  s->upd_plan.cuts.reserve(capacity / SET_UPD_PER_LAUNCH + 2);
+  s->upd_seed.assign(num_members, 0u);
+  s->upd_null.assign(num_members, 1);
   for (uint32_t g = 0; g < num_members; g++) {
+    ids[g] = g;
     rf_amd_batch* b = batches[g];
-    if (!b) {  // NULL_ROUTING_FILTER: finds nothing
-      memset(&groups[g], 0, sizeof(ProbeGroup));
-      groups[g].err = 1;
-      continue;
-    }
+    if (!b) continue;
     const uint32_t f = filter_index ? filter_index[g] : 0u;
-    if (!b->built || b->eng != e) return fail(RF_AMD_EINVAL, "member on an unbuilt or foreign batch");
-    if (f >= b->F) return fail(RF_AMD_EINVAL, "bad filter index");
+    if (int rc = check_member(e, b, f)) return rc;
     if (int rc = batch_errors(b)) return rc;
     groups[g] = probe_group_of(b, f);
-    if (!any) s->seed = b->cfg.seed;
-    else if (b->cfg.seed != s->seed) s->one_seed = false;
-    any = true;
+    s->upd_seed[g] = b->cfg.seed;
+    s->upd_null[g] = 0;
   }
-  if (s->d_groups.alloc(sizeof(ProbeGroup) * num_members, &e->pool)) return RF_AMD_ENOMEM;
-  if (num_members) {
-    HIPCHK(hipMemcpyAsync(s->d_groups.p, groups.data(), sizeof(ProbeGroup) * num_members, hipMemcpyHostToDevice,
+  // the members as one update of the empty set: its count and seed rule (the entries go up by
+  // the copy below, not by launches)
+  std::string msg;
+  if (int rc = plan_set_update(s.get(), num_members, ids.data(), s->upd_null.data(), s->upd_seed.data(),
+                               &s->upd_plan, &msg))
+    return fail(rc, msg);
+  if (s->d_groups.alloc(sizeof(ProbeGroup) * capacity, &e->pool)) return RF_AMD_ENOMEM;
+  if (capacity) {
+    HIPCHK(hipMemcpyAsync(s->d_groups.p, groups.data(), sizeof(ProbeGroup) * capacity, hipMemcpyHostToDevice,
                           e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));  // `groups` is pageable; probes may run on any stream
   }
   *out = s.release();
+  return 0;
+}
+
+extern "C" int rf_amd_filter_set_create(rf_amd_engine* e, rf_amd_batch* const* batches, const uint32_t* filter_index,
+                                        uint32_t num_members, rf_amd_filter_set** out) {
+  return filter_set_create(e, batches, filter_index, num_members, num_members, out);
+}
+
+extern "C" int rf_amd_filter_set_create_cap(rf_amd_engine* e, rf_amd_batch* const* batches,
+                                            const uint32_t* filter_index, uint32_t num_members, uint32_t capacity,
+                                            rf_amd_filter_set** out) {
+  if (out) *out = nullptr;
+  if (capacity == 0) return fail(RF_AMD_EINVAL, "capacity 0");
+  return filter_set_create(e, batches, filter_index, num_members, capacity, out);
+}
+
+extern "C" uint32_t rf_amd_filter_set_capacity(const rf_amd_filter_set* s) { return s ? s->capacity : 0; }
+
+// Members replaced in stream order: every entry is validated and the call planned on the host
+// (rf_set_plan.h) before the first launch, then ceil(entries / SET_UPD_PER_LAUNCH) launches of
+// k_set_update carry the entries in their arguments. A launch the runtime refuses comes after
+// the planner has changed the host state: the set is then undefined (rf_amd.h). The call's host
+// scratch lives in the set, so the caller serialises calls on one set. Nothing is waited for and
+// nothing allocated on the device: a member's build error is read by the kernel from the batch's
+// d_outs (which rf_amd_batch_trim keeps), behind that build on the stream; bits the host has
+// read back already (err_ready) travel with the entry.
+extern "C" int rf_amd_filter_set_update(rf_amd_filter_set* s, const uint32_t* member_id, rf_amd_batch* const* batches,
+                                        const uint32_t* filter_index, uint32_t count, void* stream) {
+  if (!s) return fail(RF_AMD_EINVAL, "null filter set");
+  if (count == 0) return 0;
+  if (!member_id || !batches) return fail(RF_AMD_EINVAL, "null member arrays");
+  s->upd_seed.resize(count);
+  s->upd_null.resize(count);
+  for (uint32_t i = 0; i < count; i++) {
+    const rf_amd_batch* b = batches[i];
+    if (int rc = check_member(s->eng, b, filter_index ? filter_index[i] : 0u)) return rc;
+    s->upd_null[i] = b ? 0 : 1;
+    s->upd_seed[i] = b ? b->cfg.seed : 0u;
+  }
+  HIPCHK(hipSetDevice(s->eng->device));
+  std::string msg;
+  if (int rc = plan_set_update(s, count, member_id, s->upd_null.data(), s->upd_seed.data(), &s->upd_plan, &msg))
+    return fail(rc, msg);
+  (void)hipGetLastError();
+  const SetUpdatePlan& plan = s->upd_plan;
+  SetUpdate a{};
+  a.groups = s->d_groups.as<ProbeGroup>();
+  a.cap = s->capacity;
+  for (uint32_t l = 0; l < plan.launches(); l++) {
+    a.n = plan.cuts[l + 1] - plan.cuts[l];
+    for (uint32_t k = 0; k < a.n; k++) {
+      const uint32_t i = plan.order[plan.cuts[l] + k];
+      SetUpdEntry& en = a.e[k];
+      rf_amd_batch* b = batches[i];
+      en.id = member_id[i];
+      en.pad = 0;
+      if (!b) {
+        en.g = null_group();
+        en.out = nullptr;
+        continue;
+      }
+      const uint32_t f = filter_index ? filter_index[i] : 0u;
+      const uint32_t known = b->err_ready.load(std::memory_order_acquire) ? b->err_host[f] : 0u;
+      en.g = probe_group_with(b, f, known);
+      en.out = b->d_outs.as<FilterOut>() + f;
+    }
+    if (int rc = rf_launch_set_update(stream ? stream : s->eng->stream, &a))
+      return fail(RF_AMD_EINVAL, std::string("set update launch: ") + hipGetErrorString((hipError_t)rc));
+  }
   return 0;
 }
 
@@ -2051,6 +2154,30 @@ extern "C" void rf_amd_filter_set_destroy(rf_amd_filter_set* s) {
   (void)hipSetDevice(s->eng->device);
   (void)hipDeviceSynchronize();
   delete s;
+}
+
+// stream-ordered destroy, as rf_amd_batch_destroy_on: every probe and update of the set is
+// ordered before the current end of `stream`; the table's block is parked behind an event
+// recorded there. Returns without waiting.
+extern "C" int rf_amd_filter_set_destroy_on(rf_amd_filter_set* s, void* stream) {
+  if (!s) return 0;
+  HIPCHK(hipSetDevice(s->eng->device));
+  hipStream_t st = stream ? (hipStream_t)stream : s->eng->stream;
+  DevPool::Parked k{};
+  hipError_t he = hipEventCreateWithFlags(&k.ev, hipEventDisableTiming);
+  if (he == hipSuccess) he = hipEventRecord(k.ev, st);
+  if (he != hipSuccess) {  // fall back to the synchronising destroy
+    if (k.ev) (void)hipEventDestroy(k.ev);
+    rf_amd_filter_set_destroy(s);
+    return 0;
+  }
+  if (s->d_groups.p) {
+    k.blocks.emplace_back(s->d_groups.p, s->d_groups.pool == &s->eng->pool ? s->d_groups.n : 0);
+    s->d_groups.p = nullptr;
+  }
+  s->eng->pool.park(std::move(k));
+  delete s;
+  return 0;
 }
 
 extern "C" uint32_t rf_amd_filter_set_num_members(const rf_amd_filter_set* s) { return s ? s->num_members : 0; }

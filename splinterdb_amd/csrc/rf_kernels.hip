@@ -4774,6 +4774,34 @@ extern "C" int rf_launch_probe_fanout_ragged(void* stream, int kind, const void*
   return e == hipSuccess ? 0 : (int)e;
 }
 
+// ---- multi-get: member updates of a resident filter set ---------------------------------
+// rf_amd_filter_set_update: lane i stores entry i of the launch into its slot of the set's
+// ProbeGroup table, in stream order -- a probe queued before the launch reads the old member,
+// one queued after it the new. The entries are the kernel's arguments (SetUpdate, rf_plan.h).
+// The member's build error is read here, from the FilterOut its build wrote earlier on the
+// stream (the host has not waited for that build), and ORed with the bits the host knew. The
+// host sends no id twice in one launch and none >= cap.
+static_assert(SET_UPD_PER_LAUNCH <= WAVE, "one lane per entry, one wave per launch");
+__global__ __launch_bounds__(WAVE) void k_set_update(SetUpdate a) {
+  const uint32_t lane = threadIdx.x;
+  if (lane >= a.n) return;
+  const SetUpdEntry& e = a.e[lane];
+  const uint32_t id = e.id;
+  if (id >= a.cap) return;
+  ProbeGroup g = e.g;
+  const FilterOut* out = e.out;
+  if (out) g.err |= out->error;
+  a.groups[id] = g;
+}
+
+extern "C" int rf_launch_set_update(void* stream, const SetUpdate* a) {
+  if (a->n == 0) return 0;
+  if (a->n > SET_UPD_PER_LAUNCH) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_set_update, dim3(1), dim3(WAVE), 0, (hipStream_t)stream, *a);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : (int)e;
+}
+
 // ---- the lookup server ---------------------------------------------------------------------
 // One persistent wave answers single lookups (routing_filter_lookup, routing_filter_lookup_async
 // states) that the host writes into a ring of SrvReq (rf_plan.h: device memory written through

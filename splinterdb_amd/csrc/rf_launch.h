@@ -61,6 +61,8 @@ int rf_launch_probe_fanout(void* stream, int kind, const void* in0, const uint64
 int rf_launch_probe_fanout_ragged(void* stream, int kind, const void* in0, const uint64_t* offs, uint32_t key_len,
                                   uint32_t seed, const rf::ProbeGroup* groups, uint32_t ng, const uint32_t* member,
                                   const uint64_t* moff, uint64_t n, uint64_t* found);
+// k_set_update: a->n <= SET_UPD_PER_LAUNCH entries into the table a->groups, one launch
+int rf_launch_set_update(void* stream, const rf::SetUpdate* a);
 // diagnostics (rf_amd_diag_fanout_max_blocks): a cap on both fan-out grids; 0 = none
 void rf_fanout_set_max_blocks(uint32_t blocks);
 uint64_t rf_found_compact_tiles(uint64_t m);

@@ -195,6 +195,29 @@ struct SmallProbe {
   uint32_t* done_flag;  // pinned host memory: seq once every result is visible
 };
 
+// member updates of a resident filter set (k_set_update) travel in the kernel arguments too: no
+// staging buffer, no copy command, nothing whose lifetime the host would have to track. An
+// entry is the member's host-resolved table entry -- g.err holding the error bits the host
+// already knows (0: none) -- the slot it goes to, and where the member's build leaves its error
+// bits, read on the device in stream order (nullptr: a NULL member, which is the all-zero
+// entry with err = 1)
+constexpr uint32_t SET_UPD_PER_LAUNCH = 64;
+struct SetUpdEntry {
+  ProbeGroup g;
+  uint32_t id;
+  uint32_t pad;
+  const FilterOut* out;
+};
+struct SetUpdate {
+  ProbeGroup* groups;  // the set's table
+  uint32_t n;          // entries of this launch
+  uint32_t cap;        // the table's entries: an id >= cap is not stored
+  SetUpdEntry e[SET_UPD_PER_LAUNCH];
+};
+static_assert(sizeof(SetUpdEntry) == 56, "40 bytes of ProbeGroup, the id, the error word's address");
+static_assert(sizeof(SetUpdate) == 16 + 56 * SET_UPD_PER_LAUNCH && sizeof(SetUpdate) <= 4096,
+              "one launch's entries fit HIP's 4,096 bytes of kernel arguments");
+
 struct LaunchArgs {
   void* stream;
   int kind;

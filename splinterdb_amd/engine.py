@@ -64,6 +64,8 @@ EXPORTED = [
     "rf_amd_diag_fanout_max_blocks", "rf_amd_diag_lookup_paths", "rf_amd_diag_part16_builds",
     "rf_amd_filter_set_probe_keys_ragged", "rf_amd_filter_set_probe_var_keys_ragged",
     "rf_amd_filter_set_probe_hashes_ragged",
+    "rf_amd_filter_set_create_cap", "rf_amd_filter_set_capacity", "rf_amd_filter_set_update",
+    "rf_amd_filter_set_destroy_on",
 ]
 ROUTE_MAX_WORLD = 16
 FOUND_COMPACT_TILE = 4096  # found words per workgroup of rf_amd_found_compact (FC_TILE)
@@ -239,6 +241,11 @@ def load_library(build_if_missing=True):
     L.rf_amd_filter_set_destroy.restype = None
     L.rf_amd_filter_set_num_members.argtypes = [vp]
     L.rf_amd_filter_set_num_members.restype = u32
+    L.rf_amd_filter_set_create_cap.argtypes = [vp, vp, vp, u32, u32, ctypes.POINTER(vp)]
+    L.rf_amd_filter_set_capacity.argtypes = [vp]
+    L.rf_amd_filter_set_capacity.restype = u32
+    L.rf_amd_filter_set_update.argtypes = [vp, vp, vp, vp, u32, vp]
+    L.rf_amd_filter_set_destroy_on.argtypes = [vp, vp]
     L.rf_amd_filter_set_probe_keys.argtypes = [vp, vp, u32, vp, u32, u64, vp, vp]
     L.rf_amd_filter_set_probe_hashes.argtypes = [vp, vp, vp, u32, u64, vp, vp]
     L.rf_amd_found_compact_scratch_bytes.argtypes = [u64]
@@ -964,10 +971,27 @@ def diag_fanout_max_blocks(blocks: int):
 
 class FilterSet:
     """A resident table of filters of any batches (rf_amd_filter_set): members = [(FilterBatch,
-    index) or None]. The member batches must outlive the set's last probe."""
+    index) or None]. The member batches must outlive the set's last probe. capacity (None: the
+    number of members) is the room update() has: the slots past the members start empty."""
 
-    def __init__(self, members, engine=None):
+    def __init__(self, members, engine=None, capacity=None):
         self.engine = engine or default_engine()
+        n = len(members)
+        hs, idx = self._member_arrays(members)
+        h = ctypes.c_void_p()
+        if capacity is None:
+            _check(load_library().rf_amd_filter_set_create(self.engine.h, ctypes.addressof(hs), idx.ctypes.data, n,
+                                                           ctypes.byref(h)))
+        else:
+            _check(load_library().rf_amd_filter_set_create_cap(self.engine.h, ctypes.addressof(hs), idx.ctypes.data,
+                                                               n, int(capacity), ctypes.byref(h)))
+        self.h = h
+        self.num_members = n
+        self._members = list(members) + [None] * (self.capacity - n)  # slot -> (batch, index) or None
+        self._keep = [m[0] for m in self._members if m is not None]
+
+    @staticmethod
+    def _member_arrays(members):
         n = len(members)
         hs = (ctypes.c_void_p * max(1, n))()
         idx = np.zeros(max(1, n), dtype=np.uint32)
@@ -975,16 +999,47 @@ class FilterSet:
             if m is not None:
                 hs[i] = m[0].h.value
                 idx[i] = m[1]
-        self._keep = [m[0] for m in members if m is not None]
-        self.num_members = n
-        h = ctypes.c_void_p()
-        _check(load_library().rf_amd_filter_set_create(self.engine.h, ctypes.addressof(hs), idx.ctypes.data, n,
-                                                       ctypes.byref(h)))
-        self.h = h
+        return hs, idx
+
+    @property
+    def capacity(self):
+        return load_library().rf_amd_filter_set_capacity(self.h)
+
+    def update(self, ids, members, stream=None):
+        """rf_amd_filter_set_update: slot ids[i] becomes members[i] -- (FilterBatch, index), or
+        None to clear it -- in stream order, without a host wait (the caller orders the members'
+        builds before the call, on the same stream or with an event). An id named twice: the
+        last entry wins. num_members follows the call. Returns what slot ids[i] held before the
+        call, entry by entry; the set references the new batches afterwards and the replaced ones
+        no longer, so the caller keeps the returned members alive until the last probe ordered
+        before the update has run (dropping a FilterBatch synchronises the device, which is safe;
+        FilterBatch.close(stream) after the update is the release without a wait)."""
+        ids = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+        members = list(members)
+        if len(members) != ids.size:
+            raise ValueError("ids and members differ in length")
+        hs, idx = self._member_arrays(members)
+        L = load_library()
+        _check(L.rf_amd_filter_set_update(self.h, ids.ctypes.data if ids.size else None,
+                                          ctypes.addressof(hs) if ids.size else None, idx.ctypes.data, ids.size,
+                                          _stream(stream)))
+        replaced = [self._members[int(i)] for i in ids]
+        for i, m in zip(ids, members):
+            self._members[int(i)] = m
+        self._keep = [m[0] for m in self._members if m is not None]
+        self.num_members = L.rf_amd_filter_set_num_members(self.h)
+        return replaced
 
     def close(self):
         if getattr(self, "h", None):
             load_library().rf_amd_filter_set_destroy(self.h)
+            self.h = None
+
+    def close_on(self, stream):
+        """rf_amd_filter_set_destroy_on: release the set in stream order (every probe and update
+        of it must be ordered before the current end of `stream`), without a wait"""
+        if getattr(self, "h", None):
+            _check(load_library().rf_amd_filter_set_destroy_on(self.h, _stream(stream)))
             self.h = None
 
     def __del__(self):

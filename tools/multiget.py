@@ -27,9 +27,20 @@ K = 4 lists through both kernels. The non-padded words of (a) and (b), and both 
 are compared before anything is timed. Default output: profiles/multiget_ragged.json
 (profiles/multiget_var_ragged.json).
 
+--update: what a compaction does to a resident set of --filters members (any number; each filter
+of --keys hashes), two ways: (a) rf_amd_filter_set_update of u = 1, 16 and 256 members (clamped to
+the set's size) and (b) rf_amd_filter_set_destroy plus rf_amd_filter_set_create of the whole set.
+After each way one small probe runs (n = 4,096, K = 4); both ways' words after the same change are
+compared before anything is timed. Reported per way and u, minimum to maximum over the
+alternating rounds: the host wall time of the call or calls (the C calls alone: both ways'
+argument arrays are built beforehand), and the HIP-event time from before the call to after the
+probe (the stream is idle at the first event, so this interval contains the host time). Default output: profiles/multiget_update.json (measured with
+--filters 1024 --keys 4096).
+
     timeout -k 10 600 python tools/multiget.py [--var] [--ragged] [--filters 64] [--keys 1048576]
                                                [--n 16777216] [--k 4] [--rounds 7] [--warmup 2]
                                                [--out profiles/multiget.json]
+    timeout -k 10 300 python tools/multiget.py --update --filters 1024 --keys 4096
 """
 import argparse
 import json
@@ -159,6 +170,146 @@ def ragged(args, fset, eng, stream, kin, own, mean_len, timed, rng):
     return out
 
 
+def update_mode(args):
+    """--update: a compaction's change to a resident set, two ways; see the module docstring"""
+    import ctypes
+    import time
+
+    import numpy as np
+    F, nk, n, Kf = args.filters, args.keys, 4096, 4
+    dev = torch.device("cuda:0")
+    cfg = E.routing_config_init(fingerprint_size=26, log_index_size=8, seed=42)
+    eng = E.Engine(0)
+    L = E.load_library()
+    stream = torch.cuda.Stream(device=dev)
+    st = stream.cuda_stream
+    with torch.cuda.stream(stream):
+        g = torch.Generator(device=dev)
+        g.manual_seed(7)
+        # base: the set's members; alt: the filters compactions replace them with (other keys, other values)
+        h_base = torch.randint(-(1 << 31), 1 << 31, (F, nk), device=dev, generator=g).to(torch.int32)
+        h_alt = torch.randint(-(1 << 31), 1 << 31, (F, nk), device=dev, generator=g).to(torch.int32)
+        base = E.FilterBatch(cfg, [nk] * F, [f % 32 for f in range(F)], engine=eng)
+        alt = E.FilterBatch(cfg, [nk] * F, [32 + f % 32 for f in range(F)], engine=eng)
+        base.build_hashes(h_base, stream=st)
+        alt.build_hashes(h_alt, stream=st)
+        assert not any(i.error for i in base.infos(stream=st)) and not any(i.error for i in alt.infos(stream=st))
+        # probe i: a hash of base or alt filter i % F (so a replaced member answers differently), in Kf random members
+        # of which the first is its own filter
+        pick = torch.randint(0, nk, (n,), device=dev, generator=g)
+        own = torch.arange(n, device=dev) % F
+        ph = torch.where(torch.arange(n, device=dev) % 2 == 0, h_base[own, pick], h_alt[own, pick]).contiguous()
+        member = torch.randint(0, F, (n, Kf), device=dev, generator=g)
+        member[:, 0] = own
+        member = member.to(torch.int32).contiguous()
+        found = torch.zeros(n * Kf, dtype=torch.int64, device=dev)
+    stream.synchronize()
+
+    ptrs = {"base": (ctypes.c_void_p * F)(*[base.h.value] * F), "alt": (ctypes.c_void_p * F)(*[alt.h.value] * F)}
+    index = np.arange(F, dtype=np.uint32)
+    hset = ctypes.c_void_p()
+
+    us = sorted({min(u, F) for u in (1, 16, 256)})
+    # way (b)'s member arrays, built here like way (a)'s: the timed region holds the C calls only.
+    # (first_u, name): the first first_u members from batch `name`, the others from base
+    whole = {(u, name): (ctypes.c_void_p * F)(*([ptrs[name][0]] * u + [base.h.value] * (F - u)))
+             for u in [0] + us for name in ("base", "alt")}
+    whole_addr = {k: ctypes.addressof(v) for k, v in whole.items()}
+    eng_h, index_addr, hset_ref = eng.h, index.ctypes.data, ctypes.byref(hset)
+    ptrs_addr = {k: ctypes.addressof(v) for k, v in ptrs.items()}
+
+    def create(first_u, name):
+        E._check(L.rf_amd_filter_set_create(eng_h, whole_addr[first_u, name], index_addr, F, hset_ref))
+
+    def way_update(u, name):
+        E._check(L.rf_amd_filter_set_update(hset, index_addr, ptrs_addr[name], index_addr, u, st))
+
+    def way_recreate(u, name):
+        L.rf_amd_filter_set_destroy(hset)
+        create(u, name)
+
+    def probe():
+        E._check(L.rf_amd_filter_set_probe_hashes(hset, ph.data_ptr(), member.data_ptr(), Kf, n, found.data_ptr(), st))
+
+    def timed(way, u, name):
+        """(host microseconds of the call or calls, HIP-event milliseconds from before them to after the probe)"""
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(stream)
+        t0 = time.perf_counter()
+        way(u, name)
+        host = time.perf_counter() - t0
+        probe()
+        b.record(stream)
+        stream.synchronize()
+        return host * 1e6, a.elapsed_time(b)
+
+    def rng(v):
+        return {"min": round(min(v), 4), "max": round(max(v), 4), "rounds": [round(x, 4) for x in v]}
+
+    def versus(a, b):
+        return {"ranges_touch": not (max(a) < min(b) or max(b) < min(a)),
+                "update_faster_beyond_ranges": bool(max(a) < min(b)),
+                "update_slower_beyond_ranges": bool(max(b) < min(a))}
+
+    create(0, "base")
+    # both ways' words after the same change, compared before anything is timed
+    for u in us:
+        words = {}
+        for wname, way in (("update", way_update), ("recreate", way_recreate)):
+            way(u, "alt")
+            probe()
+            stream.synchronize()
+            words[wname] = found.clone()
+            way(u, "base")
+        assert torch.equal(words["update"], words["recreate"]), ("the two ways disagree", u)
+        hit = (words["update"].view(n, Kf)[:, 0] != 0)
+        even = torch.arange(n, device=dev) % 2 == 0
+        assert bool(hit[even & (own >= u)].all()) and bool(hit[~even & (own < u)].all()), "false negative"
+    res = {}
+    for u in us:
+        t = {"update": ([], []), "recreate": ([], [])}
+        for r in range(args.warmup + args.rounds):
+            name = "alt" if r % 2 == 0 else "base"
+            for wname, way in (("update", way_update), ("recreate", way_recreate)):  # alternating
+                host, ev = timed(way, u, name)
+                if r >= args.warmup:
+                    t[wname][0].append(host)
+                    t[wname][1].append(ev)
+        res[str(u)] = {
+            "update_host_us": rng(t["update"][0]), "recreate_host_us": rng(t["recreate"][0]),
+            "update_event_ms": rng(t["update"][1]), "recreate_event_ms": rng(t["recreate"][1]),
+            "host": versus(t["update"][0], t["recreate"][0]),
+            "event": versus(t["update"][1], t["recreate"][1]),
+        }
+    L.rf_amd_filter_set_destroy(hset)
+    out = {
+        "what": ("a compaction's change to a resident set of F members, two ways: (a) rf_amd_filter_set_update of u "
+                 "members, (b) rf_amd_filter_set_destroy + rf_amd_filter_set_create of the whole set; after each, one "
+                 "probe_hashes of n hashes in K members. host_us: wall time of the call or calls; event_ms: HIP events "
+                 "on the launch stream from before the call to after the probe; the stream is idle when the first "
+                 "event is recorded, so this interval contains the host time of the call and is not a second, "
+                 "independent figure. Both ways' argument arrays are built before the timed region: it holds the C "
+                 "calls (through ctypes) only. Alternating rounds in one process"),
+        "config": {"filters": F, "keys_per_filter": nk, "n": n, "K": Kf, "rounds": args.rounds, "warmup": args.warmup,
+                   "fingerprint_size": 26, "log_index_size": 8},
+        "u": res,
+        "update_faster_beyond_ranges": all(r["host"]["update_faster_beyond_ranges"] and
+                                           r["event"]["update_faster_beyond_ranges"] for r in res.values()),
+        "update_slower_beyond_ranges": any(r["host"]["update_slower_beyond_ranges"] or
+                                           r["event"]["update_slower_beyond_ranges"] for r in res.values()),
+        "verified": "both ways' n K words equal after the same change, for every u; every probe of its own filter found",
+        "device": torch.cuda.get_device_name(0),
+    }
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as fh:
+        json.dump(out, fh, indent=1)
+        fh.write("\n")
+    print(json.dumps(out))
+    base.close()
+    alt.close()
+    eng.close()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--filters", type=int, default=64)
@@ -169,13 +320,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--var", action="store_true", help="variable-length keys (8-100 B)")
     ap.add_argument("--ragged", action="store_true", help="per-key member lists: ragged against padded to K = 16")
+    ap.add_argument("--update", action="store_true",
+                    help="member updates of a resident set against destroy + create of the whole set")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
         name = "multiget" + ("_var" if args.var else "") + ("_ragged" if args.ragged else "") + ".json"
-        args.out = os.path.join(ROOT, "profiles", name)
+        args.out = os.path.join(ROOT, "profiles", "multiget_update.json" if args.update else name)
     if not torch.cuda.is_available():
         sys.exit("multiget.py measures on the GPU: no HIP device")
+    if args.update:
+        return update_mode(args)
     F, nk, n, Kf = args.filters, args.keys, args.n, args.k
     assert 1 <= F <= 64, "one value per filter: at most 64 filters"
     dev = torch.device("cuda:0")
