@@ -2,7 +2,11 @@
 // the invariants the kernels rely on, on the smallest inputs that reach each branch. Built
 // and run by tests/test_batch_plan.py; needs no device. Prints "ref <lis> <n> <lnb>
 // <num_indices> <vs>" lines for that test to compare with the CPU oracle, then "plan_check: OK".
+// Each argument fp:lis:n:value:sigma adds a "line <fp> <lis> <n> <value> <sigma> <lg_line> <lnb>
+// <rem> <vs> <rvs>" row: the probe geometry the planner gives a fresh filter of n fingerprints
+// under PlanKnobs::line_sigma = sigma (tests/test_probe_geometry_cases.py).
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include <string>
@@ -405,7 +409,27 @@ static void check_line_sigma() {
   CHECK(b.plans[0].lg_line <= a.plans[0].lg_line && b.NL >= a.NL);
 }
 
-int main() {
+// one "line" row per argument fp:lis:n:value:sigma (sigma is echoed as given)
+static void print_line_rows(int argc, char** argv) {
+  for (int i = 1; i < argc; i++) {
+    unsigned fp, lis, n, value;
+    char sigma[64];
+    if (sscanf(argv[i], "%u:%u:%u:%u:%63s", &fp, &lis, &n, &value, sigma) != 5) {
+      printf("bad argument %s\n", argv[i]);
+      g_failed++;
+      continue;
+    }
+    PlanKnobs k;
+    k.line_sigma = atof(sigma);
+    BatchPlan b;
+    CHECK(plan1(config(fp, lis), n, (uint16_t)value, &b, nullptr, k) == 0);
+    if (b.plans.empty()) continue;
+    const FilterPlan& p = b.plans[0];
+    printf("line %u %u %u %u %s %u %u %u %u %u\n", fp, lis, n, value, sigma, p.lg_line, p.lnb, p.rem, p.vs, p.rvs);
+  }
+}
+
+int main(int argc, char** argv) {
   check_fresh_geometry();
   check_binsh();
   check_value_width();
@@ -421,6 +445,7 @@ int main() {
       CHECK(plan1(config(26, lis), n, 0, &b) == 0);
       printf("ref %u %u %u %u %u\n", lis, n, b.plans[0].lnb, b.plans[0].num_indices, b.plans[0].vs);
     }
+  print_line_rows(argc, argv);
   if (g_failed) {
     printf("plan_check: %d checks FAILED\n", g_failed);
     return 1;

@@ -20,14 +20,19 @@ SRC = os.path.join(ROOT, "tests", "c", "plan_check.cpp")
 EXE = os.path.join(ROOT, "tests", "c", "plan_check")
 
 
-@pytest.fixture(scope="module")
-def plan_check_output():
+def run_plan_check(args=()):
+    """plan_check's output (built first when its sources are newer); args: its "line" rows"""
     deps = [SRC, os.path.join(CSRC, "rf_batch_plan.h"), os.path.join(CSRC, "rf_plan.h")]
     if not os.path.exists(EXE) or any(os.path.getmtime(d) > os.path.getmtime(EXE) for d in deps):
         subprocess.run([HIPCC, "-x", "hip", "--offload-arch=gfx950", "-std=c++17", "-I", CSRC, SRC, "-o", EXE], check=True)
-    r = subprocess.run([EXE], capture_output=True, text=True, timeout=60)
+    r = subprocess.run([EXE, *args], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0, r.stdout[-4000:] + r.stderr[-2000:]
     return r.stdout
+
+
+@pytest.fixture(scope="module")
+def plan_check_output():
+    return run_plan_check()
 
 
 def test_planner_invariants(plan_check_output):

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLD
+from probe_geometry_cases import expected_probe_lines
 from splinterdb_amd import engine as E
 from splinterdb_amd import keys as K
 
@@ -338,36 +339,6 @@ def test_probe_line_overflow_falls_back_to_image(oracle):
         want = of.lookup_hashes(ph)
         assert (got == want).all(), (lis, int((got != want).sum()))
         assert (got[: P // 3] >> np.uint64(value) & np.uint64(1)).all()
-
-
-def expected_probe_lines(pages, slots, num_indices, IS, G, rvs):
-    """numpy restatement of the device-only probe-line format (rf_kernels.hip, "probe
-    lines"), cut from a filter image: per group of G buckets, bits [0,128) the group's slice
-    of the unary encoding (zero padded; all ones = overflow), bits [128,512) its packed
-    remainders."""
-    bits = np.unpackbits(pages, bitorder="little")
-    L = IS // G
-    out = np.zeros((num_indices * L, 64), dtype=np.uint8)
-    for i in range(num_indices):
-        h = int(slots[i])
-        c = int(pages[h]) | (int(pages[h + 1]) << 8)
-        e0 = (h + 2) * 8
-        enc = bits[e0: e0 + c + IS]
-        ones = np.flatnonzero(enc)
-        r0 = (h + 2 + (c + IS - 1) // 8 + 4) * 8
-        for g in range(L):
-            a = 0 if g == 0 else int(ones[g * G - 1]) + 1
-            end = int(ones[g * G + G - 1]) + 1
-            ne = end - a
-            n, E = ne - G, a - g * G
-            line = np.zeros(512, dtype=np.uint8)
-            if ne > 128 or n * rvs > 384:
-                line[:128] = 1
-            else:
-                line[:ne] = enc[a:end]
-                line[128:128 + n * rvs] = bits[r0 + E * rvs: r0 + (E + n) * rvs]
-            out[i * L + g] = np.packbits(line, bitorder="little")
-    return out
 
 
 def _check_lines(b, img, cfg_kw, value):
