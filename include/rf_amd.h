@@ -313,6 +313,65 @@ uint64_t rf_amd_found_compact_scratch_bytes(uint64_t m);
 int rf_amd_found_compact(rf_amd_engine *e, const uint64_t *d_found, uint64_t m,
                          uint64_t *d_cand, uint64_t cap, uint64_t *d_count,
                          void *d_scratch, void *stream);
+/* ---- range maps: multi-get keys routed to their member lists on the device ----------------
+ * What produces the ragged probe's per-key lists. At each node on its trunk path a key takes
+ * the last pivot whose key is <= it (trunk_ondisk_node_find_pivot, src/trunk.c:5886-5932,
+ * less_than_or_equal under data_key_compare) and from it the node's live inflight bundles and the
+ * pivot bundle (trunk_merge_lookup, src/trunk.c:6275-6330). Flattened over the levels, the pivot
+ * keys of all nodes cut the key space into R ranges; every key of one range has the same member
+ * list, the concatenation along its path. A range map is that table, resident on the device;
+ * a route call is an upper-bound search of each key in it and the expansion of the range's list
+ * into the CSR that rf_amd_filter_set_probe_*_ragged reads, so a multi-get runs route, ragged
+ * probe, rf_amd_found_compact from raw device keys without the host touching a key.
+ * The order is the default data_config's: slice_lex_cmp (src/util.h:67-81), unsigned memcmp over
+ * the common length, then the shorter key first. A custom key_compare is not supported.
+ *
+ * create: R = num_ranges >= 1 ranges cut by R - 1 boundary keys: boundary j is
+ * h_bound_bytes[h_bound_off[j] .. h_bound_off[j+1]) (R offsets; NULL allowed when R == 1),
+ * strictly ascending under slice_lex_cmp. Range r holds the keys k with
+ * boundary[r-1] <= k < boundary[r] (range 0: k < boundary[0]; range R-1: k >= boundary[R-2]),
+ * i.e. r = the number of boundaries <= k. Range r's member list is
+ * h_list[h_list_off[r] .. h_list_off[r+1]) (R + 1 non-decreasing uint64 offsets, h_list_off[0]
+ * any value; ids are member ids of whatever filter set the caller probes, not validated).
+ * Validated on the host, EINVAL before anything is allocated: num_ranges == 0, NULL arrays where
+ * needed, boundary offsets decreasing, boundaries not strictly ascending (equal ones included),
+ * list offsets decreasing, a list longer than 65,535 ids (the ragged probe's limit). The table
+ * is then copied into pool memory on the engine stream and that stream synchronised, as
+ * rf_amd_filter_set_create does. A map is immutable: a trunk change makes a new map and
+ * releases the old one with destroy_on behind the route calls that read it (their output is a
+ * copy: nothing downstream reads the map). A map holds no reference to any set or batch.
+ * destroy synchronises the device; destroy_on is stream-ordered and does not wait (NULL: OK). */
+typedef struct rf_amd_range_map rf_amd_range_map;
+int  rf_amd_range_map_create(rf_amd_engine *e, uint32_t num_ranges, const uint8_t *h_bound_bytes,
+                             const uint64_t *h_bound_off, const uint32_t *h_list,
+                             const uint64_t *h_list_off, rf_amd_range_map **out);
+void rf_amd_range_map_destroy(rf_amd_range_map *m);
+int  rf_amd_range_map_destroy_on(rf_amd_range_map *m, void *stream);
+uint32_t rf_amd_range_map_num_ranges(const rf_amd_range_map *m);
+uint32_t rf_amd_range_map_max_list(const rf_amd_range_map *m); /* longest list: n * max_list bounds the pairs */
+/* route: d_range[i] = key i's range; d_member_off receives n + 1 offsets, d_member_off[0] = 0,
+ * key i owning the pairs [d_member_off[i], d_member_off[i+1]); d_member[p] holds the ids of key
+ * i's range list in list order; *d_total = d_member_off[n]. The offsets and *d_total are always
+ * the true values, also when they exceed pair_cap; nothing is written at or past
+ * d_member[pair_cap) (pair_cap == 0: d_member may be NULL). A caller that sizes pair_cap =
+ * n * rf_amd_range_map_max_list(m) never overflows and can queue the ragged probe behind the
+ * call without reading anything back. Asynchronous on stream (NULL = the engine's), three
+ * launches, no allocation, no synchronisation: d_scratch (8-byte aligned) holds
+ * rf_amd_range_route_scratch_bytes(n) bytes (callable without a device; non-decreasing in n). The
+ * same input gives the same bytes. Keys form: any key_len > 0, any alignment. Var form: key i is
+ * d_bytes[d_offsets[i] .. d_offsets[i+1]); d_offsets[0] need not be 0, zero-length keys are
+ * legal, a key may have any length. n == 0 is OK: it writes d_member_off[0] = 0 and
+ * *d_total = 0 and nothing else. EINVAL: a NULL map, key_len == 0, n >= 2^56, a NULL
+ * d_member_off or d_total, and with n > 0 a NULL input, d_range or d_scratch, or a NULL d_member
+ * with pair_cap > 0. */
+uint64_t rf_amd_range_route_scratch_bytes(uint64_t n);
+int rf_amd_range_map_route_keys(rf_amd_range_map *m, const void *d_keys, uint32_t key_len, uint64_t n,
+                                uint32_t *d_range, uint64_t *d_member_off, uint32_t *d_member,
+                                uint64_t pair_cap, uint64_t *d_total, void *d_scratch, void *stream);
+int rf_amd_range_map_route_var_keys(rf_amd_range_map *m, const uint8_t *d_bytes, const uint64_t *d_offsets,
+                                    uint64_t n, uint32_t *d_range, uint64_t *d_member_off,
+                                    uint32_t *d_member, uint64_t pair_cap, uint64_t *d_total,
+                                    void *d_scratch, void *stream);
 /* The engine's lookup server: single lookups -- routing_filter_lookup (src/routing_filter.h:
  * 87-92) and routing_filter_lookup_async states (:130-155) -- without a kernel launch per
  * call. A persistent wave (started on demand on a queue of its own, exiting after 400 us

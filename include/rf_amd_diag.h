@@ -81,8 +81,18 @@ uint64_t rf_amd_diag_part16_builds(void);
 /* process-wide cap on the grid of the fan-out probe (rf_amd_filter_set_probe_*), in workgroups
  * of 256 keys; 0 restores the default, a grid that covers n. With a cap below n / 256 every
  * wave takes several 64-key chunks, so a test of a few thousand keys runs the kernel's
- * grid-stride loop, which otherwise starts only above 2^31 workgroups. Always returns 0. */
+ * grid-stride loop, which otherwise starts only above 2^31 workgroups. Always returns 0.
+ * The route kernels of a range map (rf_amd_range_map_route_*) honour the same cap, in workgroups
+ * of one tile of rf_amd_diag_range_tile() keys: capped at 1 or 2, a call over three tiles runs
+ * every one of their loops more than once per workgroup. */
 int rf_amd_diag_fanout_max_blocks(uint32_t blocks);
+
+/* range maps: the keys of one scan tile of a route call (the unit of its scratch and of its
+ * grid-stride loops), and the largest num_ranges whose boundary prefixes the search keeps in LDS
+ * -- a map with more ranges is searched through L2 by another instance of the kernel, so a test
+ * takes one map on each side of it. Both are constants of the build. */
+uint32_t rf_amd_diag_range_tile(void);
+uint32_t rf_amd_diag_range_lds_ranges(void);
 
 /* the source id the library was built from (16 hex digits of SHA-256 over the engine's
  * sources and headers, splinterdb_amd/build.py source_id): the Python loader refuses a

@@ -2255,6 +2255,7 @@ extern "C" int rf_amd_filter_set_probe_hashes_ragged(rf_amd_filter_set* s, const
 
 extern "C" int rf_amd_diag_fanout_max_blocks(uint32_t blocks) {
   rf_fanout_set_max_blocks(blocks);
+  rf_range_set_max_blocks(blocks);
   return 0;
 }
 
@@ -2276,6 +2277,116 @@ extern "C" int rf_amd_found_compact(rf_amd_engine* e, const uint64_t* d_found, u
   int rc = rf_launch_found_compact(stream ? stream : e->stream, d_found, m, d_cand, cap, d_count, d_scratch);
   if (rc) return fail(RF_AMD_EINVAL, std::string("compaction launch: ") + hipGetErrorString((hipError_t)rc));
   return 0;
+}
+
+// ---- range maps: multi-get keys routed to their member lists --------------------------------
+// The map is the planner's image (rf_range_plan.h) in one pool block, immutable; a route call is
+// three launches over it and the caller's buffers (rf_range.hip). It holds no reference to any
+// set or batch, and nothing downstream reads it: the route output is a copy.
+struct rf_amd_range_map {
+  rf_amd_engine* eng = nullptr;
+  uint32_t num_ranges = 0, max_list = 0;
+  DevBuf d_image;
+  RangeDev dev{};
+};
+
+extern "C" int rf_amd_range_map_create(rf_amd_engine* e, uint32_t num_ranges, const uint8_t* h_bound_bytes,
+                                       const uint64_t* h_bound_off, const uint32_t* h_list,
+                                       const uint64_t* h_list_off, rf_amd_range_map** out) {
+  if (!e) return fail(RF_AMD_ENODEV, "no engine");
+  if (!out) return fail(RF_AMD_EINVAL, "null out-param");
+  *out = nullptr;
+  RangePlan plan;
+  std::string msg;
+  if (int rc = plan_range_map(num_ranges, h_bound_bytes, h_bound_off, h_list, h_list_off, &plan, &msg))
+    return fail(rc, msg);
+  HIPCHK(hipSetDevice(e->device));
+  auto m = std::make_unique<rf_amd_range_map>();
+  m->eng = e;
+  m->num_ranges = plan.num_ranges;
+  m->max_list = plan.max_list;
+  if (m->d_image.alloc(plan.image.size(), &e->pool)) return RF_AMD_ENOMEM;
+  HIPCHK(hipMemcpyAsync(m->d_image.p, plan.image.data(), plan.image.size(), hipMemcpyHostToDevice, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));  // the image is pageable; route calls may run on any stream
+  const uint8_t* base = m->d_image.as<uint8_t>();
+  m->dev.num_ranges = plan.num_ranges;
+  m->dev.prefix = reinterpret_cast<const uint64_t*>(base + plan.o_prefix);
+  m->dev.boff = reinterpret_cast<const uint64_t*>(base + plan.o_boff);
+  m->dev.loff = reinterpret_cast<const uint64_t*>(base + plan.o_loff);
+  m->dev.list = reinterpret_cast<const uint32_t*>(base + plan.o_list);
+  m->dev.bytes = base + plan.o_bytes;
+  *out = m.release();
+  return 0;
+}
+
+// synchronises the device (route calls on a caller's stream may still read the image), as
+// rf_amd_filter_set_destroy does
+extern "C" void rf_amd_range_map_destroy(rf_amd_range_map* m) {
+  if (!m) return;
+  (void)hipSetDevice(m->eng->device);
+  (void)hipDeviceSynchronize();
+  delete m;
+}
+
+// stream-ordered destroy, as rf_amd_filter_set_destroy_on: the image's block is parked behind an
+// event recorded on `stream`. Returns without waiting.
+extern "C" int rf_amd_range_map_destroy_on(rf_amd_range_map* m, void* stream) {
+  if (!m) return 0;
+  HIPCHK(hipSetDevice(m->eng->device));
+  hipStream_t st = stream ? (hipStream_t)stream : m->eng->stream;
+  DevPool::Parked k{};
+  hipError_t he = hipEventCreateWithFlags(&k.ev, hipEventDisableTiming);
+  if (he == hipSuccess) he = hipEventRecord(k.ev, st);
+  if (he != hipSuccess) {  // fall back to the synchronising destroy
+    if (k.ev) (void)hipEventDestroy(k.ev);
+    rf_amd_range_map_destroy(m);
+    return 0;
+  }
+  if (m->d_image.p) {
+    k.blocks.emplace_back(m->d_image.p, m->d_image.pool == &m->eng->pool ? m->d_image.n : 0);
+    m->d_image.p = nullptr;
+  }
+  m->eng->pool.park(std::move(k));
+  delete m;
+  return 0;
+}
+
+extern "C" uint32_t rf_amd_range_map_num_ranges(const rf_amd_range_map* m) { return m ? m->num_ranges : 0; }
+extern "C" uint32_t rf_amd_range_map_max_list(const rf_amd_range_map* m) { return m ? m->max_list : 0; }
+extern "C" uint64_t rf_amd_range_route_scratch_bytes(uint64_t n) { return range_route_scratch_bytes(n); }
+extern "C" uint32_t rf_amd_diag_range_lds_ranges(void) { return RANGE_LDS_RANGES; }
+extern "C" uint32_t rf_amd_diag_range_tile(void) { return RANGE_TILE; }
+
+static int range_route(rf_amd_range_map* m, int var, const uint8_t* in0, const uint64_t* offs, uint32_t key_len,
+                       uint64_t n, uint32_t* d_range, uint64_t* d_member_off, uint32_t* d_member, uint64_t pair_cap,
+                       uint64_t* d_total, void* d_scratch, void* stream) {
+  if (!m) return fail(RF_AMD_EINVAL, "null range map");
+  if (n >= (1ull << 56)) return fail(RF_AMD_EINVAL, "n >= 2^56");
+  if (!d_member_off || !d_total) return fail(RF_AMD_EINVAL, "null member offsets / total");
+  if (n && (!in0 || (var && !offs) || !d_range || !d_scratch)) return fail(RF_AMD_EINVAL, "null route buffer");
+  if (n && pair_cap && !d_member) return fail(RF_AMD_EINVAL, "null member buffer");
+  if ((uintptr_t)d_scratch & 7) return fail(RF_AMD_EINVAL, "scratch not 8-byte aligned");
+  HIPCHK(hipSetDevice(m->eng->device));
+  (void)hipGetLastError();
+  int rc = rf_launch_range_route(stream ? stream : m->eng->stream, var, in0, offs, key_len, n, &m->dev, d_range,
+                                 d_member_off, d_member, pair_cap, d_total, d_scratch);
+  if (rc) return fail(RF_AMD_EINVAL, std::string("range route launch: ") + hipGetErrorString((hipError_t)rc));
+  return 0;
+}
+
+extern "C" int rf_amd_range_map_route_keys(rf_amd_range_map* m, const void* d_keys, uint32_t key_len, uint64_t n,
+                                           uint32_t* d_range, uint64_t* d_member_off, uint32_t* d_member,
+                                           uint64_t pair_cap, uint64_t* d_total, void* d_scratch, void* stream) {
+  if (key_len == 0) return fail(RF_AMD_EINVAL, "key_len 0");
+  return range_route(m, 0, static_cast<const uint8_t*>(d_keys), nullptr, key_len, n, d_range, d_member_off,
+                     d_member, pair_cap, d_total, d_scratch, stream);
+}
+extern "C" int rf_amd_range_map_route_var_keys(rf_amd_range_map* m, const uint8_t* d_bytes,
+                                               const uint64_t* d_offsets, uint64_t n, uint32_t* d_range,
+                                               uint64_t* d_member_off, uint32_t* d_member, uint64_t pair_cap,
+                                               uint64_t* d_total, void* d_scratch, void* stream) {
+  return range_route(m, 1, d_bytes, d_offsets, 0, n, d_range, d_member_off, d_member, pair_cap, d_total,
+                     d_scratch, stream);
 }
 
 static int do_probe(rf_amd_batch* b, int kind, const void* in0, const uint64_t* offs, uint32_t key_len,

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "rf_plan.h"
+#include "rf_range_plan.h"
 
 extern "C" {
 
@@ -69,6 +70,16 @@ uint64_t rf_found_compact_tiles(uint64_t m);
 // scratch: ntiles 64-bit offsets, then ntiles 32-bit sums
 int rf_launch_found_compact(void* stream, const uint64_t* found, uint64_t m, uint64_t* cand, uint64_t cap,
                             uint64_t* count, void* scratch);
+
+// ---- range maps (rf_range.hip) --------------------------------------------------------------
+// k_range_find, k_range_scan, k_range_emit: n keys (var: keys[offs[i] .. offs[i+1]), else
+// key_len bytes each) to range[n], member_off[n + 1], member[< pair_cap] and *total; scratch:
+// range_route_scratch_bytes(n) bytes, 8-byte aligned
+int rf_launch_range_route(void* stream, int var, const uint8_t* keys, const uint64_t* offs, uint32_t key_len,
+                          uint64_t n, const rf::RangeDev* m, uint32_t* range, uint64_t* member_off,
+                          uint32_t* member, uint64_t pair_cap, uint64_t* total, void* scratch);
+// diagnostics (rf_amd_diag_fanout_max_blocks): a cap on the route kernels' grids; 0 = none
+void rf_range_set_max_blocks(uint32_t blocks);
 
 // ---- estimate, hashing, routing, verify ---------------------------------------------------
 // bitmap (zeroed by the caller, bitmap_words a multiple of 4) -> counters[0] = entries

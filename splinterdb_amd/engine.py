@@ -66,6 +66,10 @@ EXPORTED = [
     "rf_amd_filter_set_probe_hashes_ragged",
     "rf_amd_filter_set_create_cap", "rf_amd_filter_set_capacity", "rf_amd_filter_set_update",
     "rf_amd_filter_set_destroy_on",
+    "rf_amd_range_map_create", "rf_amd_range_map_destroy", "rf_amd_range_map_destroy_on",
+    "rf_amd_range_map_num_ranges", "rf_amd_range_map_max_list", "rf_amd_range_route_scratch_bytes",
+    "rf_amd_range_map_route_keys", "rf_amd_range_map_route_var_keys",
+    "rf_amd_diag_range_tile", "rf_amd_diag_range_lds_ranges",
 ]
 ROUTE_MAX_WORLD = 16
 FOUND_COMPACT_TILE = 4096  # found words per workgroup of rf_amd_found_compact (FC_TILE)
@@ -259,6 +263,22 @@ def load_library(build_if_missing=True):
     L.rf_amd_filter_set_probe_var_keys_ragged.argtypes = [vp, vp, vp, vp, vp, u64, vp, vp]
     L.rf_amd_filter_set_probe_hashes_ragged.argtypes = [vp, vp, vp, vp, u64, vp, vp]
     L.rf_amd_diag_fanout_max_blocks.argtypes = [u32]
+    L.rf_amd_range_map_create.argtypes = [vp, u32, vp, vp, vp, vp, ctypes.POINTER(vp)]
+    L.rf_amd_range_map_destroy.argtypes = [vp]
+    L.rf_amd_range_map_destroy.restype = None
+    L.rf_amd_range_map_destroy_on.argtypes = [vp, vp]
+    L.rf_amd_range_map_num_ranges.argtypes = [vp]
+    L.rf_amd_range_map_num_ranges.restype = u32
+    L.rf_amd_range_map_max_list.argtypes = [vp]
+    L.rf_amd_range_map_max_list.restype = u32
+    L.rf_amd_range_route_scratch_bytes.argtypes = [u64]
+    L.rf_amd_range_route_scratch_bytes.restype = u64
+    L.rf_amd_range_map_route_keys.argtypes = [vp, vp, u32, u64, vp, vp, vp, u64, vp, vp, vp]
+    L.rf_amd_range_map_route_var_keys.argtypes = [vp, vp, vp, u64, vp, vp, vp, u64, vp, vp, vp]
+    L.rf_amd_diag_range_tile.argtypes = []
+    L.rf_amd_diag_range_tile.restype = u32
+    L.rf_amd_diag_range_lds_ranges.argtypes = []
+    L.rf_amd_diag_range_lds_ranges.restype = u32
     L.rf_amd_host_alloc.argtypes = [vp, u64, ctypes.POINTER(vp)]
     L.rf_amd_host_free.argtypes = [vp, vp]
     L.rf_amd_host_free.restype = None
@@ -1131,6 +1151,36 @@ class FilterSet:
                                    right=True) - 1
         return d_cand, count, d_key
 
+    def multiget_routed(self, range_map, d_keys, key_len, n, cap=None, stream=None):
+        """RangeMap.route_keys + probe_keys_ragged + found_compact, from raw device keys: returns
+        (d_cand, count, d_key) as multiget_ragged does, the pairs being those of the route call's
+        CSR (first offset 0). One 8-byte read of the pair count sizes d_found, in the place of
+        multiget_ragged's read of the offsets; then as multiget."""
+        return self._multiget_routed(
+            n, cap, stream, lambda: range_map.route_keys(d_keys, key_len, n, stream=stream),
+            lambda d_member, d_off, d_found: self.probe_keys_ragged(d_keys, key_len, d_member, d_off, n, d_found,
+                                                                    stream))
+
+    def multiget_var_routed(self, range_map, d_bytes, d_offsets, n, cap=None, stream=None):
+        """multiget_routed for variable-length keys (route_var_keys + probe_var_keys_ragged)"""
+        return self._multiget_routed(
+            n, cap, stream, lambda: range_map.route_var_keys(d_bytes, d_offsets, n, stream=stream),
+            lambda d_member, d_off, d_found: self.probe_var_keys_ragged(d_bytes, d_offsets, d_member, d_off, n,
+                                                                        d_found, stream))
+
+    def _multiget_routed(self, n, cap, stream, route, probe):
+        import torch
+        d_range, d_off, d_member, d_total = route()
+        if stream is not None:  # a raw handle torch's own copy is not ordered with
+            torch.cuda.ExternalStream(stream).synchronize()
+        m = int(d_total.item())  # the one read
+        d_found = torch.empty(m, dtype=torch.int64, device=d_off.device)
+        if m:
+            probe(d_member, d_off, d_found)
+        d_cand, count = self._compact_found(d_found, m, 1, max(1, n) if cap is None else cap, stream)
+        d_key = torch.searchsorted(d_off[:n + 1], d_cand[:count] >> 8, right=True) - 1
+        return d_cand, count, d_key
+
     def _compact_found(self, d_found, n, K, cap, stream):
         """the multi-get's tail: the candidates of d_found[:n * K] as (d_cand, count)"""
         import torch
@@ -1149,3 +1199,124 @@ class FilterSet:
             found_compact(d_found, n * K, d_cand, d_count, stream, self.engine)
             count = read_count()
         return d_cand, count
+
+
+# ---- range maps: multi-get keys routed to their member lists -----------------------------
+def range_route_host(boundaries, lists, keys):
+    """Host mirror of a route call (rf_amd_range_map_route_*): boundaries = the R - 1 boundary
+    keys as `bytes`, strictly ascending; lists = the R id sequences; keys = n `bytes`. Key i's
+    range is the number of boundaries <= it -- bisect_right, Python's `bytes` order being
+    slice_lex_cmp's (unsigned bytes over the common length, then the shorter first). Returns
+    (range uint32[n], member_off uint64[n + 1], member uint32[total], total)."""
+    import bisect
+    boundaries = [bytes(b) for b in boundaries]
+    if len(lists) != len(boundaries) + 1:
+        raise ValueError("R lists take R - 1 boundaries")
+    rng = np.fromiter((bisect.bisect_right(boundaries, bytes(k)) for k in keys), dtype=np.uint32, count=len(keys))
+    llen = np.array([len(x) for x in lists], dtype=np.int64)
+    loff = np.zeros(len(lists) + 1, dtype=np.int64)
+    np.cumsum(llen, out=loff[1:])
+    flat = np.fromiter((i for x in lists for i in x), dtype=np.uint32, count=int(loff[-1]))
+    cnt = llen[rng]
+    off = np.zeros(len(keys) + 1, dtype=np.uint64)
+    np.cumsum(cnt.astype(np.uint64), out=off[1:])
+    total = int(off[-1])
+    # pair p of key i is id p - off[i] of its range's list
+    key = np.repeat(np.arange(len(keys), dtype=np.int64), cnt)
+    src = loff[rng][key] + (np.arange(total, dtype=np.int64) - off[:-1].astype(np.int64)[key])
+    return rng, off, flat[src], total
+
+
+def diag_range_tile() -> int:
+    """keys per scan tile of a route call (rf_amd_diag_range_tile)"""
+    return int(load_library().rf_amd_diag_range_tile())
+
+
+def diag_range_lds_ranges() -> int:
+    """the largest R whose boundary prefixes the route kernel searches in LDS
+    (rf_amd_diag_range_lds_ranges); a map with more ranges takes the kernel's other instance"""
+    return int(load_library().rf_amd_diag_range_lds_ranges())
+
+
+def range_route_scratch_bytes(n) -> int:
+    return int(load_library().rf_amd_range_route_scratch_bytes(n))
+
+
+_route_scratch = {}  # (engine, stream) -> the scratch of the last route call issued there
+
+
+class RangeMap:
+    """A resident, immutable table of R key ranges and their member lists (rf_amd_range_map):
+    boundaries = the R - 1 boundary keys as `bytes`, strictly ascending in `bytes` order; lists =
+    R sequences of member ids (of whatever FilterSet the caller probes), each of at most 65,535.
+    Range r holds the keys k with boundaries[r-1] <= k < boundaries[r]."""
+
+    def __init__(self, boundaries, lists, engine=None):
+        self.engine = engine or default_engine()
+        boundaries = [bytes(b) for b in boundaries]
+        R = len(lists)
+        if R != len(boundaries) + 1:
+            raise ValueError("R lists take R - 1 boundaries")
+        boff = np.zeros(max(R, 1), dtype=np.uint64)
+        np.cumsum(np.array([len(b) for b in boundaries], dtype=np.uint64), out=boff[1:R])
+        bbytes = np.frombuffer(b"".join(boundaries) + b"\0", dtype=np.uint8)
+        loff = np.zeros(R + 1, dtype=np.uint64)
+        np.cumsum(np.array([len(x) for x in lists], dtype=np.uint64), out=loff[1:])
+        flat = np.fromiter((i for x in lists for i in x), dtype=np.uint32, count=int(loff[-1]))
+        flat = np.ascontiguousarray(np.append(flat, np.uint32(0)))
+        h = ctypes.c_void_p()
+        _check(load_library().rf_amd_range_map_create(self.engine.h, R, bbytes.ctypes.data, boff.ctypes.data,
+                                                      flat.ctypes.data, loff.ctypes.data, ctypes.byref(h)))
+        self.h = h
+        self.num_ranges = R
+        self.max_list = int(load_library().rf_amd_range_map_max_list(h))
+
+    def close(self):
+        if getattr(self, "h", None):
+            load_library().rf_amd_range_map_destroy(self.h)
+            self.h = None
+
+    def close_on(self, stream):
+        """rf_amd_range_map_destroy_on: release the map in stream order (every route call on it
+        must be ordered before the current end of `stream`), without a wait. What the route
+        calls wrote stays valid: it is a copy."""
+        if getattr(self, "h", None):
+            _check(load_library().rf_amd_range_map_destroy_on(self.h, _stream(stream)))
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _route(self, call, n, pair_cap, stream, device):
+        import torch
+        st = _stream(stream)
+        cap = n * self.max_list if pair_cap is None else int(pair_cap)
+        d_range = torch.empty(n, dtype=torch.int32, device=device)
+        d_off = torch.empty(n + 1, dtype=torch.int64, device=device)
+        d_member = torch.empty(cap, dtype=torch.int32, device=device)
+        d_total = torch.empty(1, dtype=torch.int64, device=device)
+        scratch = torch.empty(range_route_scratch_bytes(n) // 8, dtype=torch.int64, device=device)
+        _check(call(d_range.data_ptr() if n else None, d_off.data_ptr(), d_member.data_ptr() if cap else None, cap,
+                    d_total.data_ptr(), scratch.data_ptr(), st))
+        _route_scratch[(id(self.engine), st)] = scratch
+        return d_range, d_off, d_member, d_total
+
+    def route_keys(self, d_keys, key_len, n, pair_cap=None, stream=None):
+        """rf_amd_range_map_route_keys: n fixed-length device keys to (d_range int32[n],
+        d_member_off int64[n + 1], d_member int32[pair_cap], d_total int64[1]), asynchronously:
+        key i's range, and the CSR of the ranges' lists that probe_keys_ragged reads. pair_cap
+        None: n * the map's longest list, which never overflows; the offsets and the total are
+        the true values whatever pair_cap is."""
+        L = load_library()
+        return self._route(lambda *a: L.rf_amd_range_map_route_keys(self.h, _dptr(d_keys), key_len, n, *a),
+                           n, pair_cap, stream, getattr(d_keys, "device", "cuda"))
+
+    def route_var_keys(self, d_bytes, d_offsets, n, pair_cap=None, stream=None):
+        """route_keys for variable-length keys: key i is d_bytes[d_offsets[i] : d_offsets[i+1]]"""
+        L = load_library()
+        return self._route(lambda *a: L.rf_amd_range_map_route_var_keys(self.h, _dptr(d_bytes), _dptr(d_offsets),
+                                                                        n, *a),
+                           n, pair_cap, stream, getattr(d_offsets, "device", "cuda"))

@@ -27,6 +27,19 @@ K = 4 lists through both kernels. The non-padded words of (a) and (b), and both 
 are compared before anything is timed. Default output: profiles/multiget_ragged.json
 (profiles/multiget_var_ragged.json).
 
+--routed: the multi-get from raw device keys, on the --ragged shape (with --var:
+variable-length keys). A range map (E.RangeMap) of R = 4,096 ranges, cut by boundaries drawn from
+the key population (one per 8-byte prefix), each range with a list of min(16, 1 + Geometric(1/3))
+random members. Timed with the same method: (a) the route call alone
+(rf_amd_range_map_route_keys: keys to ranges and the CSR of their lists), (b) route + ragged probe
++ compaction, (c) ragged probe + compaction from a precomputed CSR (what a caller had before, re-
+measured in the same run), and (d) the host alternative, by the wall clock: keys D2H into pinned
+memory, routing by np.searchsorted over big-endian 8-byte prefixes (valid because the boundaries'
+prefixes are unique and every key has 8 bytes), the CSR by numpy, and its H2D. (a)'s ranges are
+compared with the host mirror (E.range_route_host) on a sample of 2^16 keys and, with its offsets,
+ids and total, with (d)'s whole result before anything is timed. Default output:
+profiles/multiget_routed.json (profiles/multiget_var_routed.json).
+
 --update: what a compaction does to a resident set of --filters members (any number; each filter
 of --keys hashes), two ways: (a) rf_amd_filter_set_update of u = 1, 16 and 256 members (clamped to
 the set's size) and (b) rf_amd_filter_set_destroy plus rf_amd_filter_set_create of the whole set.
@@ -37,7 +50,7 @@ argument arrays are built beforehand), and the HIP-event time from before the ca
 probe (the stream is idle at the first event, so this interval contains the host time). Default output: profiles/multiget_update.json (measured with
 --filters 1024 --keys 4096).
 
-    timeout -k 10 600 python tools/multiget.py [--var] [--ragged] [--filters 64] [--keys 1048576]
+    timeout -k 10 600 python tools/multiget.py [--var] [--ragged | --routed] [--filters 64] [--keys 1048576]
                                                [--n 16777216] [--k 4] [--rounds 7] [--warmup 2]
                                                [--out profiles/multiget.json]
     timeout -k 10 300 python tools/multiget.py --update --filters 1024 --keys 4096
@@ -167,6 +180,185 @@ def ragged(args, fset, eng, stream, kin, own, mean_len, timed, rng):
     }
     if args.var:
         out["config"]["mean_key_len"] = round(mean_len, 3)
+    return out
+
+
+ROUTED_R = 4096  # --routed: ranges of the map
+
+
+def routed(args, fset, eng, stream, kin, timed, rng):
+    """--routed: (a) route, (b) route + ragged probe + compaction, (c) ragged probe + compaction
+    from a precomputed CSR, (d) the host alternative to (a); kin: the keys' arguments"""
+    import time
+
+    import numpy as np
+    F, n, R = args.filters, args.n, ROUTED_R
+    st = stream.cuda_stream
+    dev = kin[0].device
+    L = E.load_library()
+    hr = np.random.default_rng(11)
+    probe_r = fset.probe_var_keys_ragged if args.var else fset.probe_keys_ragged
+
+    # keys to the host once (pinned), as (d) does every round
+    def keys_to_host(pins):
+        with torch.cuda.stream(stream):
+            for p, d in zip(pins, kin if args.var else kin[:1]):
+                p.copy_(d.reshape(-1), non_blocking=True)
+        stream.synchronize()
+
+    pins = [torch.empty(x.numel(), dtype=x.dtype, pin_memory=True) for x in (kin if args.var else kin[:1])]
+    keys_to_host(pins)
+
+    def prefixes(pins):
+        """every key's first 8 bytes as a big-endian uint64 (a strided view of the pinned bytes)"""
+        b = pins[0].numpy()
+        if args.var:
+            return np.ndarray((b.size - 7,), dtype=">u8", buffer=b.data, strides=(1,))[pins[1].numpy()[:-1]]
+        return np.ndarray((n,), dtype=">u8", buffer=b.data, strides=(24,))
+
+    def key_bytes(i):
+        if args.var:
+            o = pins[1].numpy()
+            return bytes(pins[0].numpy()[int(o[i]):int(o[i + 1])])
+        return bytes(pins[0].numpy()[24 * i:24 * i + 24])
+
+    # R - 1 boundaries from the key population, one per 8-byte prefix
+    pre = prefixes(pins)
+    cand = hr.choice(n, size=2 * R, replace=False)
+    _, first = np.unique(pre[cand], return_index=True)
+    cand = cand[np.sort(first)][:R - 1]
+    assert cand.size == R - 1, "too few keys with distinct prefixes"
+    bounds = sorted(key_bytes(int(i)) for i in cand)
+    bpre = np.array([int.from_bytes(b[:8], "big") for b in bounds], dtype=np.uint64)
+    assert (bpre[1:] > bpre[:-1]).all()
+    llen = np.minimum(KPAD, 1 + hr.geometric(1.0 / 3.0, size=R)).astype(np.int64)
+    loff = np.zeros(R + 1, dtype=np.int64)
+    np.cumsum(llen, out=loff[1:])
+    flat = hr.integers(0, F, size=int(loff[-1])).astype(np.uint32)
+    lists = [flat[loff[r]:loff[r + 1]].tolist() for r in range(R)]
+    rmap = E.RangeMap(bounds, lists, engine=eng)
+    assert rmap.max_list <= KPAD
+    pair_cap = n * rmap.max_list
+
+    def host_route(pins):
+        """(d)'s compute: ranges by searchsorted over the prefixes, then the CSR"""
+        rg = np.searchsorted(bpre, prefixes(pins), side="right").astype(np.uint32)
+        cnt = llen[rg]
+        off = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(cnt, out=off[1:])
+        key = np.repeat(np.arange(n, dtype=np.int64), cnt)
+        src = loff[rg][key] + (np.arange(int(off[-1]), dtype=np.int64) - off[:-1][key])
+        return rg, off, flat[src]
+
+    with torch.cuda.stream(stream):
+        d_range = torch.zeros(n, dtype=torch.int32, device=dev)
+        d_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        d_member = torch.zeros(pair_cap, dtype=torch.int32, device=dev)
+        d_total = torch.zeros(1, dtype=torch.int64, device=dev)
+        scratch = torch.zeros(E.range_route_scratch_bytes(n) // 8, dtype=torch.int64, device=dev)
+        d_count = torch.zeros(1, dtype=torch.int64, device=dev)
+    stream.synchronize()
+
+    def route():
+        out = (d_range.data_ptr(), d_off.data_ptr(), d_member.data_ptr(), pair_cap, d_total.data_ptr(),
+               scratch.data_ptr(), st)
+        if args.var:
+            E._check(L.rf_amd_range_map_route_var_keys(rmap.h, kin[0].data_ptr(), kin[1].data_ptr(), n, *out))
+        else:
+            E._check(L.rf_amd_range_map_route_keys(rmap.h, kin[0].data_ptr(), 24, n, *out))
+
+    # (a)'s output against the host mirror and against (d)'s result, before anything is timed
+    route()
+    stream.synchronize()
+    m = int(d_total.item())
+    rg_h, off_h, mem_h = host_route(pins)
+    assert m == int(off_h[-1]), "total differs from the host's"
+    assert np.array_equal(d_range.cpu().numpy().view(np.uint32), rg_h), "ranges differ from the host's"
+    assert np.array_equal(d_off.cpu().numpy(), off_h), "offsets differ from the host's"
+    assert np.array_equal(d_member[:m].cpu().numpy().view(np.uint32), mem_h), "ids differ from the host's"
+    sample = hr.choice(n, size=1 << 16, replace=False)
+    sample[:R - 1] = cand  # the boundaries themselves among them
+    mirror = E.range_route_host(bounds, lists, [key_bytes(int(i)) for i in sample])[0]
+    assert np.array_equal(mirror, rg_h[sample]), "ranges differ from E.range_route_host"
+    del rg_h, mem_h, mirror
+    with torch.cuda.stream(stream):
+        off_pre, member_pre = d_off.clone(), d_member[:m].clone()  # (c)'s precomputed CSR
+        found = torch.zeros(m, dtype=torch.int64, device=dev)
+        probe_r(*kin, member_pre, off_pre, n, found, stream=st)
+        E.found_compact(found, m, None, d_count, stream=st, engine=eng)
+    stream.synchronize()
+    count = int(d_count.item())
+    with torch.cuda.stream(stream):
+        d_cand = torch.zeros(max(count, 1), dtype=torch.int64, device=dev)
+        found_b = torch.zeros(m, dtype=torch.int64, device=dev)
+        h_off = torch.empty(n + 1, dtype=torch.int64, pin_memory=True)
+        h_mem = torch.empty(m, dtype=torch.int32, pin_memory=True)
+        up_off, up_mem = torch.zeros_like(off_pre), torch.zeros_like(member_pre)
+    stream.synchronize()
+
+    def routed_multiget():  # found_b is sized by the pair count read once above; the route call
+        route()             # itself needs no read: pair_cap = n * max_list
+        probe_r(*kin, d_member, d_off, n, found_b, stream=st)
+        E.found_compact(found_b, m, d_cand, d_count, stream=st, engine=eng)
+
+    def csr_multiget():
+        probe_r(*kin, member_pre, off_pre, n, found, stream=st)
+        E.found_compact(found, m, d_cand, d_count, stream=st, engine=eng)
+
+    def host_alternative():
+        stream.synchronize()
+        t0 = time.perf_counter()
+        keys_to_host(pins)
+        t1 = time.perf_counter()
+        _, off, mem = host_route(pins)
+        t2 = time.perf_counter()
+        h_off.numpy()[:] = off
+        h_mem.numpy()[:] = mem.view(np.int32)
+        with torch.cuda.stream(stream):
+            up_off.copy_(h_off, non_blocking=True)
+            up_mem.copy_(h_mem, non_blocking=True)
+        stream.synchronize()
+        t3 = time.perf_counter()
+        return [(t3 - t0) * 1e3, (t1 - t0) * 1e3, (t2 - t1) * 1e3, (t3 - t2) * 1e3]
+
+    t = {"route": [], "routed_multiget": [], "csr_multiget": [], "host_total": [], "host_d2h": [],
+         "host_compute": [], "host_h2d": []}
+    for r in range(args.warmup + args.rounds):
+        a, b, c = timed(route), timed(routed_multiget), timed(csr_multiget)
+        d = host_alternative()
+        if r >= args.warmup:
+            for w, ms in zip(t, [a, b, c] + d):
+                t[w].append(ms)
+    assert int(d_count.item()) == count and torch.equal(found, found_b) and torch.equal(up_mem, member_pre)
+    t["csr_plus_host"] = [x + y for x, y in zip(t["csr_multiget"], t["host_total"])]
+    ms = {w: rng(v) for w, v in t.items()}
+    a, b, c, cd = t["route"], t["routed_multiget"], t["csr_multiget"], t["csr_plus_host"]
+    out = {
+        "what": ("multi-get of n %s from raw device keys through a range map of R ranges (boundaries drawn from the "
+                 "keys, lists of min(16, 1 + Geometric(1/3)) random members of one batch of F filters): (a) the route "
+                 "call alone, (b) route + ragged probe + found_compact, (c) ragged probe + found_compact from a "
+                 "precomputed CSR, (d) the host alternative to (a) by the wall clock: keys D2H into pinned memory, "
+                 "np.searchsorted over big-endian 8-byte prefixes, the CSR by numpy, its H2D; alternating rounds in "
+                 "one process, HIP events on the launch stream for (a)-(c)"
+                 % ("variable-length keys (keys.var_keys, 8-100 B)" if args.var else "24-byte keys")),
+        "config": {"filters": F, "keys_per_filter": args.keys, "n": n, "ranges": R, "pairs": m,
+                   "mean_list": round(m / n, 4), "max_list": rmap.max_list, "rounds": args.rounds,
+                   "warmup": args.warmup, "fingerprint_size": 26, "log_index_size": 8},
+        "ms": ms,
+        "route_share_of_csr_multiget": {"min": round(min(a) / max(c), 4), "max": round(max(a) / min(c), 4)},
+        "routed_vs_csr_plus_host": {"ranges_touch": not (max(b) < min(cd) or max(cd) < min(b)),
+                                    "routed_faster_beyond_ranges": bool(max(b) < min(cd))},
+        "routed_minus_csr_ms": {"min": round(min(x - y for x, y in zip(b, c)), 4),
+                                "max": round(max(x - y for x, y in zip(b, c)), 4)},
+        "candidates": count,
+        "csr_bytes": 8 * (n + 1) + 4 * m,
+        "candidate_bytes": 8 * count,
+        "verified": "ranges, offsets, ids and total of (a) equal to (d)'s for all n keys; ranges equal to "
+                    "E.range_route_host for 2^16 sampled keys, every boundary key among them; found words of (b) "
+                    "and (c) equal",
+        "device": torch.cuda.get_device_name(0),
+    }
+    rmap.close()
     return out
 
 
@@ -320,12 +512,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--var", action="store_true", help="variable-length keys (8-100 B)")
     ap.add_argument("--ragged", action="store_true", help="per-key member lists: ragged against padded to K = 16")
+    ap.add_argument("--routed", action="store_true",
+                    help="route + ragged probe + compaction from raw keys through a range map")
     ap.add_argument("--update", action="store_true",
                     help="member updates of a resident set against destroy + create of the whole set")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
-        name = "multiget" + ("_var" if args.var else "") + ("_ragged" if args.ragged else "") + ".json"
+        name = "multiget" + ("_var" if args.var else "") + ("_ragged" if args.ragged else "") + \
+            ("_routed" if args.routed else "") + ".json"
         args.out = os.path.join(ROOT, "profiles", "multiget_update.json" if args.update else name)
     if not torch.cuda.is_available():
         sys.exit("multiget.py measures on the GPU: no HIP device")
@@ -404,10 +599,13 @@ def main():
     def rng(v):
         return {"min": round(min(v), 4), "max": round(max(v), 4), "rounds": [round(x, 4) for x in v]}
 
-    if args.ragged:
+    if args.ragged or args.routed:
         del found_a, found_b, member
         kin = (d_bytes, d_offs) if args.var else (keys, 24)
-        out = ragged(args, fset, eng, stream, kin, own, mean_len, timed, rng)
+        if args.routed:
+            out = routed(args, fset, eng, stream, kin, timed, rng)
+        else:
+            out = ragged(args, fset, eng, stream, kin, own, mean_len, timed, rng)
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as fh:
             json.dump(out, fh, indent=1)
