@@ -7,6 +7,12 @@ namespace rf {
 
 constexpr int WAVE = 64;
 
+// a launcher's return value: 0, or the HIP error of the launches since the caller cleared it
+inline int launch_status() {
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : (int)e;
+}
+
 // ---- XXH32 (published xxHash algorithm; the reference's platform_hash32,
 //      src/platform_linux/platform_hash.h:23) ----------------------------------------
 // The global-memory hash helpers also compile for the host (tests/c/hash_check.cpp runs them
@@ -279,6 +285,34 @@ __device__ __forceinline__ uint32_t block_excl_scan(uint32_t x, uint32_t* s_tmp,
   *total = s_tmp[NW];
   __syncthreads();
   return r;
+}
+
+// The workgroup's sum of c, returned to thread 0 (other threads: unspecified). s_c needs NT/64
+// words. Contains barriers, the last one after thread 0 has read s_c (the caller may call again
+// at once): call from every thread.
+template <int NT>
+__device__ __forceinline__ uint32_t block_sum(uint32_t c, uint32_t* s_c) {
+  c = wave_incl_scan(c);
+  if ((threadIdx.x & (WAVE - 1)) == WAVE - 1) s_c[threadIdx.x / WAVE] = c;
+  __syncthreads();
+  uint32_t s = 0;
+  if (threadIdx.x == 0)
+    for (int w = 0; w < NT / WAVE; w++) s += s_c[w];
+  __syncthreads();
+  return s;
+}
+
+// The owner of pair p among a wave's 64 keys: the last k with off[k] <= p, by a 6-step search of
+// the wave's row of pair offsets parked in LDS (the caller has synchronised). off[0] == 0, so
+// every p has an owner, and an empty list (off[k] == off[k + 1]) owns no pair. The entries of
+// dead keys (past a partial wave's last key) hold the row's pair count, so no p below it names
+// them; p at or past the count finds some key below 64, whose data the caller must not use.
+__device__ __forceinline__ uint32_t wave_owner_of(const uint32_t* off, uint32_t p) {
+  uint32_t k = 0;
+#pragma unroll
+  for (uint32_t w = WAVE / 2; w >= 1; w >>= 1)
+    if (off[k + w] <= p) k += w;
+  return k;
 }
 
 // In-place exclusive scan of x[k] over the elements j = k * NT + threadIdx.x (k-major

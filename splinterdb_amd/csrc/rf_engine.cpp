@@ -278,6 +278,37 @@ struct DevBuf {
   T* as() const { return static_cast<T*>(p); }
 };
 
+// the stream of a call: the caller's, or the engine's own for NULL
+static hipStream_t stream_of(const rf_amd_engine* e, void* stream) { return stream ? (hipStream_t)stream : e->stream; }
+
+// a launcher's return value (rf_launch.h: 0 or a HIP error) as the call's
+static int launch_rc(const char* what, int rc) {
+  return rc ? fail(RF_AMD_EINVAL, std::string(what) + " launch: " + hipGetErrorString((hipError_t)rc)) : 0;
+}
+
+// Stream-ordered release: the live blocks of bufs[0..n) are parked behind an event recorded on
+// `st` and return to the pool (a block of another origin: to hipFree) once it has completed; the
+// buffers are left empty. Returns false, having touched no buffer, when the event could not be
+// created or recorded: the caller then releases them its own way.
+static bool park_behind(rf_amd_engine* e, hipStream_t st, DevBuf* const* bufs, size_t n) {
+  DevPool::Parked k{};
+  for (size_t i = 0; i < n; i++)
+    if (bufs[i]->p) k.blocks.emplace_back(bufs[i]->p, bufs[i]->pool == &e->pool ? bufs[i]->n : 0);
+  if (k.blocks.empty()) return true;
+  hipError_t he = hipEventCreateWithFlags(&k.ev, hipEventDisableTiming);
+  if (he == hipSuccess) he = hipEventRecord(k.ev, st);
+  if (he != hipSuccess) {
+    if (k.ev) (void)hipEventDestroy(k.ev);
+    return false;
+  }
+  for (size_t i = 0; i < n; i++) {
+    bufs[i]->p = nullptr;
+    bufs[i]->n = 0;
+  }
+  e->pool.park(std::move(k));
+  return true;
+}
+
 // every device buffer of a batch, named once: the members and bufs() (what destroy_on, trim and
 // device_bytes walk) both come from this list
 #define RF_BATCH_DEVBUFS(X)                                                                        \
@@ -688,22 +719,9 @@ extern "C" void rf_amd_batch_destroy(rf_amd_batch* b) {
 extern "C" int rf_amd_batch_destroy_on(rf_amd_batch* b, void* stream) {
   if (!b) return 0;
   HIPCHK(hipSetDevice(b->eng->device));
-  hipStream_t st = stream ? (hipStream_t)stream : b->eng->stream;
-  DevPool::Parked k{};
-  hipError_t he = hipEventCreateWithFlags(&k.ev, hipEventDisableTiming);
-  if (he == hipSuccess) he = hipEventRecord(k.ev, st);
-  if (he != hipSuccess) {  // fall back to the synchronising destroy
-    if (k.ev) (void)hipEventDestroy(k.ev);
-    rf_amd_batch_destroy(b);
-    return 0;
-  }
-  for (DevBuf* d : b->bufs()) {
-    if (!d->p) continue;
-    k.blocks.emplace_back(d->p, d->pool == &b->eng->pool ? d->n : 0);
-    d->p = nullptr;
-  }
-  b->eng->pool.park(std::move(k));
-  delete b;
+  const std::vector<DevBuf*> bufs = b->bufs();
+  if (park_behind(b->eng, stream_of(b->eng, stream), bufs.data(), bufs.size())) delete b;
+  else rf_amd_batch_destroy(b);  // fall back to the synchronising destroy
   return 0;
 }
 
@@ -716,26 +734,20 @@ extern "C" int rf_amd_batch_trim(rf_amd_batch* b, void* stream) {
   HIPCHK(hipSetDevice(b->eng->device));
   DevBuf* keep[] = {&b->d_plans, &b->d_pplans, &b->d_outs, &b->d_pages, &b->d_slots, &b->d_lines,
                     &b->d_idx_filter, &b->d_runs, &b->d_wave_tab};
-  DevPool::Parked k{};
-  for (DevBuf* d : b->bufs()) {
-    if (!d->p || std::find(std::begin(keep), std::end(keep), d) != std::end(keep)) continue;
-    k.blocks.emplace_back(d->p, d->pool == &b->eng->pool ? d->n : 0);
-    d->p = nullptr;
-    d->n = 0;
-  }
+  std::vector<DevBuf*> drop;
+  for (DevBuf* d : b->bufs())
+    if (d->p && std::find(std::begin(keep), std::end(keep), d) == std::end(keep)) drop.push_back(d);
   b->has_entries = false;
-  if (k.blocks.empty()) return 0;
-  hipStream_t st = stream ? (hipStream_t)stream : b->eng->stream;
-  hipError_t he = hipEventCreateWithFlags(&k.ev, hipEventDisableTiming);
-  if (he == hipSuccess) he = hipEventRecord(k.ev, st);
-  if (he != hipSuccess) {  // cannot order the release: wait, then release
-    if (k.ev) (void)hipEventDestroy(k.ev);
+  hipStream_t st = stream_of(b->eng, stream);
+  if (!park_behind(b->eng, st, drop.data(), drop.size())) {  // cannot order the release: wait, then release
     (void)hipStreamSynchronize(st);
     std::lock_guard<std::mutex> g(b->eng->pool.mu);
-    for (auto& blk : k.blocks) b->eng->pool.give_locked(blk.first, blk.second);
-    return 0;
+    for (DevBuf* d : drop) {
+      b->eng->pool.give_locked(d->p, d->pool == &b->eng->pool ? d->n : 0);
+      d->p = nullptr;
+      d->n = 0;
+    }
   }
-  b->eng->pool.park(std::move(k));
   return 0;
 }
 
@@ -890,12 +902,9 @@ extern "C" int rf_amd_batch_place_image(rf_amd_batch* b, uint32_t f, uint64_t* t
   void* dt = nullptr;
   HIPCHK(hipSetDevice(e->device));
   HIPCHK(hipHostGetDevicePointer(&dt, table, 0));
-  hipStream_t st = stream ? (hipStream_t)stream : e->stream;
-  const int rc = rf_launch_place(st, b->d_pages.as<uint8_t>() + (uint64_t)p.page_base * P,
-                                 b->d_slots.as<uint64_t>() + p.idx_base, first_page, count, num_pages, nidx, P,
-                                 (const uint64_t*)dt, addrs_per_page);
-  if (rc) return fail(RF_AMD_EINVAL, std::string("place launch: ") + hipGetErrorString((hipError_t)rc));
-  return 0;
+  return launch_rc("place", rf_launch_place(stream_of(e, stream), b->d_pages.as<uint8_t>() + (uint64_t)p.page_base * P,
+                                            b->d_slots.as<uint64_t>() + p.idx_base, first_page, count, num_pages,
+                                            nidx, P, (const uint64_t*)dt, addrs_per_page));
 }
 
 extern "C" int rf_amd_engine_pool_stats(rf_amd_engine* e, uint64_t* pooled_bytes, uint64_t* hits, uint64_t* misses) {
@@ -1026,7 +1035,7 @@ static int do_build(rf_amd_batch* b, int kind, const void* in0, const uint64_t* 
   if (!b) return fail(RF_AMD_EINVAL, "null batch");
   if (b->keys_total && !in0) return fail(RF_AMD_EINVAL, "null input");
   HIPCHK(hipSetDevice(b->eng->device));
-  hipStream_t st = stream ? (hipStream_t)stream : b->eng->stream;
+  hipStream_t st = stream_of(b->eng, stream);
   (void)hipGetLastError();  // launch checks below must see only their own errors
   if (b->ev_sets) b->ev_set = (b->ev_set + 1) % b->ev_sets;
   if (++b->lay_seq == 0) b->lay_seq = 1;
@@ -1055,15 +1064,14 @@ static int do_build(rf_amd_batch* b, int kind, const void* in0, const uint64_t* 
   if (b->wide) {
     // every old filter of the batch decoded by one launch sequence (which also marks the
     // unused tail of each old region); the new regions are written whole by the hashing pass
-    int rc = rf_launch_old_decode(&a);
-    if (rc) return fail(RF_AMD_EINVAL, std::string("old decode launch: ") + hipGetErrorString((hipError_t)rc));
+    if (int rc = launch_rc("old decode", rf_launch_old_decode(&a))) return rc;
   }
   b->err_ready.store(false, std::memory_order_release);  // a rebuild: read the new bits back
   int rc = rf_launch_build(&a);
   // counted once every kernel of the build is queued: a lookup that finds the stream idle
   // after reading this count cannot miss a build it covers
   if (st == b->eng->stream) b->eng->builds_issued.fetch_add(1, std::memory_order_acq_rel);
-  if (rc) return fail(RF_AMD_EINVAL, std::string("build launch: ") + hipGetErrorString((hipError_t)rc));
+  if (rc) return launch_rc("build", rc);
   b->counters_clean = a.self_clean != 0;  // every launch of the build went out
   if (getenv("RF_AMD_DIAG_OVERFLOW") && b->d_overflow.p) {  // diagnostics: coarse buckets handed back by K4/K4m
     uint32_t nov = 0;
@@ -1425,7 +1433,7 @@ static int srv_ensure(rf_amd_engine* e) {
                                        v.life_ticks.load())) {
     int z = 0;
     v.dead.compare_exchange_strong(z, RF_AMD_EINVAL);
-    return fail(RF_AMD_EINVAL, std::string("lookup server launch: ") + hipGetErrorString((hipError_t)rc));
+    return launch_rc("lookup server", rc);
   }
   v.launches.fetch_add(1, std::memory_order_relaxed);
   return 0;
@@ -1911,8 +1919,7 @@ static int probe_groups_host(rf_amd_engine* e, const std::vector<ProbeGroup>& gr
     sp.found = reinterpret_cast<uint64_t*>(s->h);
     sp.done_flag = s->flag;
     clk.launching();
-    if (int rc = rf_launch_probe_small(s->st, &sp))
-      return fail(RF_AMD_EINVAL, std::string("probe launch: ") + hipGetErrorString((hipError_t)rc));
+    if (int rc = launch_rc("probe", rf_launch_probe_small(s->st, &sp))) return rc;
     clk.launched();
     if (int rc = slot_wait(s, seq, false)) return rc;
     memcpy(h_found, s->h, 8 * n);
@@ -1930,10 +1937,10 @@ static int probe_groups_host(rf_amd_engine* e, const std::vector<ProbeGroup>& gr
   }
   uint64_t* found = reinterpret_cast<uint64_t*>(s->h + o_f);
   clk.launching();
-  if (int rc = rf_launch_probe_groups(s->st, reinterpret_cast<const uint32_t*>(in),
-                                      reinterpret_cast<const ProbeGroup*>(in + o_g), ng, n, found,
-                                      s->d_counter, wait == 2 ? nullptr : s->flag, seq))
-    return fail(RF_AMD_EINVAL, std::string("probe launch: ") + hipGetErrorString((hipError_t)rc));
+  if (int rc = launch_rc("probe", rf_launch_probe_groups(s->st, reinterpret_cast<const uint32_t*>(in),
+                                                         reinterpret_cast<const ProbeGroup*>(in + o_g), ng, n, found,
+                                                         s->d_counter, wait == 2 ? nullptr : s->flag, seq)))
+    return rc;
   clk.launched();
   if (int rc = slot_wait(s, seq, wait == 2)) return rc;
   memcpy(h_found, found, 8 * n);
@@ -2141,8 +2148,7 @@ extern "C" int rf_amd_filter_set_update(rf_amd_filter_set* s, const uint32_t* me
       en.g = probe_group_with(b, f, known);
       en.out = b->d_outs.as<FilterOut>() + f;
     }
-    if (int rc = rf_launch_set_update(stream ? stream : s->eng->stream, &a))
-      return fail(RF_AMD_EINVAL, std::string("set update launch: ") + hipGetErrorString((hipError_t)rc));
+    if (int rc = launch_rc("set update", rf_launch_set_update(stream_of(s->eng, stream), &a))) return rc;
   }
   return 0;
 }
@@ -2162,95 +2168,75 @@ extern "C" void rf_amd_filter_set_destroy(rf_amd_filter_set* s) {
 extern "C" int rf_amd_filter_set_destroy_on(rf_amd_filter_set* s, void* stream) {
   if (!s) return 0;
   HIPCHK(hipSetDevice(s->eng->device));
-  hipStream_t st = stream ? (hipStream_t)stream : s->eng->stream;
-  DevPool::Parked k{};
-  hipError_t he = hipEventCreateWithFlags(&k.ev, hipEventDisableTiming);
-  if (he == hipSuccess) he = hipEventRecord(k.ev, st);
-  if (he != hipSuccess) {  // fall back to the synchronising destroy
-    if (k.ev) (void)hipEventDestroy(k.ev);
-    rf_amd_filter_set_destroy(s);
-    return 0;
-  }
-  if (s->d_groups.p) {
-    k.blocks.emplace_back(s->d_groups.p, s->d_groups.pool == &s->eng->pool ? s->d_groups.n : 0);
-    s->d_groups.p = nullptr;
-  }
-  s->eng->pool.park(std::move(k));
-  delete s;
+  DevBuf* const table = &s->d_groups;
+  if (park_behind(s->eng, stream_of(s->eng, stream), &table, 1)) delete s;
+  else rf_amd_filter_set_destroy(s);  // fall back to the synchronising destroy
   return 0;
 }
 
 extern "C" uint32_t rf_amd_filter_set_num_members(const rf_amd_filter_set* s) { return s ? s->num_members : 0; }
 
+// The fixed form: key i against its K members (d_member == nullptr: all of them), d_member_off
+// nullptr. The ragged form: key i against d_member[d_member_off[i] .. d_member_off[i+1]), K
+// unused. `ragged` names the form, not d_member_off: a ragged call without offsets is refused
+// as one (after its n == 0 return), not as a fixed call with K == 0.
 static int set_probe(rf_amd_filter_set* s, int kind, const void* in0, const uint64_t* offs, uint32_t key_len,
-                     const uint32_t* d_member, uint32_t K, uint64_t n, uint64_t* d_found, void* stream) {
+                     const uint32_t* d_member, uint32_t K, const uint64_t* d_member_off, uint64_t n,
+                     uint64_t* d_found, void* stream, bool ragged) {
   if (!s) return fail(RF_AMD_EINVAL, "null filter set");
-  if (K == 0) return fail(RF_AMD_EINVAL, "K == 0");
-  if (!d_member && K != s->num_members) return fail(RF_AMD_EINVAL, "all-members form: K must equal num_members");
+  if (!ragged) {
+    if (K == 0) return fail(RF_AMD_EINVAL, "K == 0");
+    if (!d_member && K != s->num_members) return fail(RF_AMD_EINVAL, "all-members form: K must equal num_members");
+  }
   if (kind != IN_HASH && !s->one_seed) return fail(RF_AMD_EINVAL, "keys form over members with different seeds");
-  if (n > ((1ull << 56) - 1) / K) return fail(RF_AMD_EINVAL, "n * K >= 2^56");
+  if (ragged ? n >= (1ull << 56) : n > ((1ull << 56) - 1) / K)
+    return fail(RF_AMD_EINVAL, ragged ? "n >= 2^56" : "n * K >= 2^56");
   if (n == 0) return 0;
-  if (!in0 || !d_found || (kind == IN_VAR && !offs)) return fail(RF_AMD_EINVAL, "null probe buffer");
+  if (!in0 || !d_found || (kind == IN_VAR && !offs) || (ragged && (!d_member || !d_member_off)))
+    return fail(RF_AMD_EINVAL, "null probe buffer");
   HIPCHK(hipSetDevice(s->eng->device));
   (void)hipGetLastError();
-  int rc = rf_launch_probe_fanout(stream ? stream : s->eng->stream, kind, in0, offs, key_len, s->seed,
-                                  s->d_groups.as<ProbeGroup>(), s->num_members, d_member, K, n, d_found);
-  if (rc) return fail(RF_AMD_EINVAL, std::string("fan-out probe launch: ") + hipGetErrorString((hipError_t)rc));
-  return 0;
+  return launch_rc(ragged ? "ragged fan-out probe" : "fan-out probe",
+                   rf_launch_probe_fanout(stream_of(s->eng, stream), kind, in0, offs, key_len, s->seed,
+                                          s->d_groups.as<ProbeGroup>(), s->num_members, d_member, K, d_member_off, n,
+                                          d_found));
 }
 
 extern "C" int rf_amd_filter_set_probe_keys(rf_amd_filter_set* s, const void* d_keys, uint32_t key_len,
                                             const uint32_t* d_member, uint32_t K, uint64_t n, uint64_t* d_found,
                                             void* stream) {
   if (key_len == 0) return fail(RF_AMD_EINVAL, "key_len 0");
-  return set_probe(s, fixed_kind(d_keys, key_len), d_keys, nullptr, key_len, d_member, K, n, d_found, stream);
+  return set_probe(s, fixed_kind(d_keys, key_len), d_keys, nullptr, key_len, d_member, K, nullptr, n, d_found,
+                   stream, false);
 }
 extern "C" int rf_amd_filter_set_probe_var_keys(rf_amd_filter_set* s, const uint8_t* d_bytes,
                                                 const uint64_t* d_offsets, const uint32_t* d_member, uint32_t K,
                                                 uint64_t n, uint64_t* d_found, void* stream) {
-  return set_probe(s, IN_VAR, d_bytes, d_offsets, 0, d_member, K, n, d_found, stream);
+  return set_probe(s, IN_VAR, d_bytes, d_offsets, 0, d_member, K, nullptr, n, d_found, stream, false);
 }
 extern "C" int rf_amd_filter_set_probe_hashes(rf_amd_filter_set* s, const uint32_t* d_hashes, const uint32_t* d_member,
                                               uint32_t K, uint64_t n, uint64_t* d_found, void* stream) {
-  return set_probe(s, IN_HASH, d_hashes, nullptr, 4, d_member, K, n, d_found, stream);
+  return set_probe(s, IN_HASH, d_hashes, nullptr, 4, d_member, K, nullptr, n, d_found, stream, false);
 }
 
-// the ragged forms: key i against d_member[d_member_off[i] .. d_member_off[i+1])
-static int set_probe_ragged(rf_amd_filter_set* s, int kind, const void* in0, const uint64_t* offs, uint32_t key_len,
-                            const uint32_t* d_member, const uint64_t* d_member_off, uint64_t n, uint64_t* d_found,
-                            void* stream) {
-  if (!s) return fail(RF_AMD_EINVAL, "null filter set");
-  if (kind != IN_HASH && !s->one_seed) return fail(RF_AMD_EINVAL, "keys form over members with different seeds");
-  if (n >= (1ull << 56)) return fail(RF_AMD_EINVAL, "n >= 2^56");
-  if (n == 0) return 0;
-  if (!in0 || !d_member || !d_member_off || !d_found || (kind == IN_VAR && !offs))
-    return fail(RF_AMD_EINVAL, "null probe buffer");
-  HIPCHK(hipSetDevice(s->eng->device));
-  (void)hipGetLastError();
-  int rc = rf_launch_probe_fanout_ragged(stream ? stream : s->eng->stream, kind, in0, offs, key_len, s->seed,
-                                         s->d_groups.as<ProbeGroup>(), s->num_members, d_member, d_member_off, n,
-                                         d_found);
-  if (rc) return fail(RF_AMD_EINVAL, std::string("ragged fan-out probe launch: ") + hipGetErrorString((hipError_t)rc));
-  return 0;
-}
-
+// the ragged forms
 extern "C" int rf_amd_filter_set_probe_keys_ragged(rf_amd_filter_set* s, const void* d_keys, uint32_t key_len,
                                                    const uint32_t* d_member, const uint64_t* d_member_off, uint64_t n,
                                                    uint64_t* d_found, void* stream) {
   if (key_len == 0) return fail(RF_AMD_EINVAL, "key_len 0");
-  return set_probe_ragged(s, fixed_kind(d_keys, key_len), d_keys, nullptr, key_len, d_member, d_member_off, n,
-                          d_found, stream);
+  return set_probe(s, fixed_kind(d_keys, key_len), d_keys, nullptr, key_len, d_member, 0, d_member_off, n, d_found,
+                   stream, true);
 }
 extern "C" int rf_amd_filter_set_probe_var_keys_ragged(rf_amd_filter_set* s, const uint8_t* d_bytes,
                                                        const uint64_t* d_offsets, const uint32_t* d_member,
                                                        const uint64_t* d_member_off, uint64_t n, uint64_t* d_found,
                                                        void* stream) {
-  return set_probe_ragged(s, IN_VAR, d_bytes, d_offsets, 0, d_member, d_member_off, n, d_found, stream);
+  return set_probe(s, IN_VAR, d_bytes, d_offsets, 0, d_member, 0, d_member_off, n, d_found, stream, true);
 }
 extern "C" int rf_amd_filter_set_probe_hashes_ragged(rf_amd_filter_set* s, const uint32_t* d_hashes,
                                                      const uint32_t* d_member, const uint64_t* d_member_off,
                                                      uint64_t n, uint64_t* d_found, void* stream) {
-  return set_probe_ragged(s, IN_HASH, d_hashes, nullptr, 4, d_member, d_member_off, n, d_found, stream);
+  return set_probe(s, IN_HASH, d_hashes, nullptr, 4, d_member, 0, d_member_off, n, d_found, stream, true);
 }
 
 extern "C" int rf_amd_diag_fanout_max_blocks(uint32_t blocks) {
@@ -2274,9 +2260,8 @@ extern "C" int rf_amd_found_compact(rf_amd_engine* e, const uint64_t* d_found, u
   if ((uintptr_t)d_scratch & 7) return fail(RF_AMD_EINVAL, "scratch not 8-byte aligned");
   HIPCHK(hipSetDevice(e->device));
   (void)hipGetLastError();
-  int rc = rf_launch_found_compact(stream ? stream : e->stream, d_found, m, d_cand, cap, d_count, d_scratch);
-  if (rc) return fail(RF_AMD_EINVAL, std::string("compaction launch: ") + hipGetErrorString((hipError_t)rc));
-  return 0;
+  return launch_rc("compaction",
+                   rf_launch_found_compact(stream_of(e, stream), d_found, m, d_cand, cap, d_count, d_scratch));
 }
 
 // ---- range maps: multi-get keys routed to their member lists --------------------------------
@@ -2333,21 +2318,9 @@ extern "C" void rf_amd_range_map_destroy(rf_amd_range_map* m) {
 extern "C" int rf_amd_range_map_destroy_on(rf_amd_range_map* m, void* stream) {
   if (!m) return 0;
   HIPCHK(hipSetDevice(m->eng->device));
-  hipStream_t st = stream ? (hipStream_t)stream : m->eng->stream;
-  DevPool::Parked k{};
-  hipError_t he = hipEventCreateWithFlags(&k.ev, hipEventDisableTiming);
-  if (he == hipSuccess) he = hipEventRecord(k.ev, st);
-  if (he != hipSuccess) {  // fall back to the synchronising destroy
-    if (k.ev) (void)hipEventDestroy(k.ev);
-    rf_amd_range_map_destroy(m);
-    return 0;
-  }
-  if (m->d_image.p) {
-    k.blocks.emplace_back(m->d_image.p, m->d_image.pool == &m->eng->pool ? m->d_image.n : 0);
-    m->d_image.p = nullptr;
-  }
-  m->eng->pool.park(std::move(k));
-  delete m;
+  DevBuf* const image = &m->d_image;
+  if (park_behind(m->eng, stream_of(m->eng, stream), &image, 1)) delete m;
+  else rf_amd_range_map_destroy(m);  // fall back to the synchronising destroy
   return 0;
 }
 
@@ -2368,10 +2341,9 @@ static int range_route(rf_amd_range_map* m, int var, const uint8_t* in0, const u
   if ((uintptr_t)d_scratch & 7) return fail(RF_AMD_EINVAL, "scratch not 8-byte aligned");
   HIPCHK(hipSetDevice(m->eng->device));
   (void)hipGetLastError();
-  int rc = rf_launch_range_route(stream ? stream : m->eng->stream, var, in0, offs, key_len, n, &m->dev, d_range,
-                                 d_member_off, d_member, pair_cap, d_total, d_scratch);
-  if (rc) return fail(RF_AMD_EINVAL, std::string("range route launch: ") + hipGetErrorString((hipError_t)rc));
-  return 0;
+  return launch_rc("range route",
+                   rf_launch_range_route(stream_of(m->eng, stream), var, in0, offs, key_len, n, &m->dev, d_range,
+                                         d_member_off, d_member, pair_cap, d_total, d_scratch));
 }
 
 extern "C" int rf_amd_range_map_route_keys(rf_amd_range_map* m, const void* d_keys, uint32_t key_len, uint64_t n,
@@ -2395,14 +2367,12 @@ static int do_probe(rf_amd_batch* b, int kind, const void* in0, const uint64_t* 
   if (!b || !b->built) return fail(RF_AMD_EINVAL, "probe on an unbuilt batch");
   if (n && (!in0 || !(fid || d_runs) || !found)) return fail(RF_AMD_EINVAL, "null probe buffer");
   HIPCHK(hipSetDevice(b->eng->device));
-  hipStream_t st = stream ? (hipStream_t)stream : b->eng->stream;
+  hipStream_t st = stream_of(b->eng, stream);
   (void)hipGetLastError();
   LaunchArgs a = make_args(b, st);
   a.probe_runs = d_runs;
   a.wave_tab = d_runs ? b->d_wave_tab.as<uint32_t>() : nullptr;
-  int rc = rf_launch_probe(&a, kind, in0, offs, key_len, fid, n, found);
-  if (rc) return fail(RF_AMD_EINVAL, std::string("probe launch: ") + hipGetErrorString((hipError_t)rc));
-  return 0;
+  return launch_rc("probe", rf_launch_probe(&a, kind, in0, offs, key_len, fid, n, found));
 }
 
 extern "C" int rf_amd_batch_probe_keys(rf_amd_batch* b, const void* d_keys, uint32_t key_len,
@@ -2434,7 +2404,7 @@ static int upload_runs(rf_amd_batch* b, const uint64_t* h_counts, void* stream, 
   HIPCHK(hipSetDevice(b->eng->device));
   if (runs != b->runs_host) {
     if (!b->d_runs.p && b->d_runs.alloc(8ull * (b->F + 1), &b->eng->pool)) return RF_AMD_ENOMEM;
-    hipStream_t st = stream ? (hipStream_t)stream : b->eng->stream;
+    hipStream_t st = stream_of(b->eng, stream);
     HIPCHK(hipStreamSynchronize(st));  // earlier probes may still read the old bounds
     const uint64_t nw = (n + 63) / 64;
     if (b->d_wave_tab.n < 4 * nw && b->d_wave_tab.alloc(4 * nw, &b->eng->pool)) return RF_AMD_ENOMEM;
@@ -2465,14 +2435,12 @@ extern "C" int rf_amd_debug_probe_floor(rf_amd_batch* b, const void* d_in, uint3
   uint64_t n = 0;
   if (int rc = upload_runs(b, h_counts, stream, &n)) return rc;
   if (n == 0) return 0;
-  hipStream_t st = stream ? (hipStream_t)stream : b->eng->stream;
+  hipStream_t st = stream_of(b->eng, stream);
   (void)hipGetLastError();
   LaunchArgs a = make_args(b, st);
   a.probe_runs = b->d_runs.as<uint64_t>();
   a.wave_tab = b->d_wave_tab.as<uint32_t>();
-  int rc = rf_launch_probe_floor(&a, key_len == 24 ? IN_KEYS24 : IN_HASH, d_in, n, d_out);
-  if (rc) return fail(RF_AMD_EINVAL, std::string("probe floor launch: ") + hipGetErrorString((hipError_t)rc));
-  return 0;
+  return launch_rc("probe floor", rf_launch_probe_floor(&a, key_len == 24 ? IN_KEYS24 : IN_HASH, d_in, n, d_out));
 }
 
 extern "C" int rf_amd_batch_probe_keys_runs(rf_amd_batch* b, const void* d_keys, uint32_t key_len,
@@ -2517,7 +2485,7 @@ extern "C" int rf_amd_debug_rebuild_lines(rf_amd_batch* b) {
   (void)hipGetLastError();
   LaunchArgs a = make_args(b, b->eng->stream);
   a.plines_force = 1;  // every filter, also those whose lines K6 cut
-  if (int rc = rf_launch_plines(&a)) return fail(RF_AMD_EINVAL, std::string("probe-line launch: ") + hipGetErrorString((hipError_t)rc));
+  if (int rc = launch_rc("probe-line", rf_launch_plines(&a))) return rc;
   HIPCHK(hipStreamSynchronize(b->eng->stream));
   return 0;
 }
@@ -2639,7 +2607,7 @@ extern "C" int rf_amd_batch_read_image_async(rf_amd_batch* b, uint32_t f, void* 
   if (pages_bytes > (uint64_t)p.page_cap * b->cfg.page_size || num_slots > p.num_indices)
     return fail(RF_AMD_EINVAL, "copy larger than the filter's reservation");
   HIPCHK(hipSetDevice(b->eng->device));
-  hipStream_t st = stream ? (hipStream_t)stream : b->eng->stream;
+  hipStream_t st = stream_of(b->eng, stream);
   if (h_pages && pages_bytes)
     HIPCHK(hipMemcpyAsync(h_pages, b->d_pages.as<uint8_t>() + (uint64_t)p.page_base * b->cfg.page_size,
                           pages_bytes, hipMemcpyDeviceToHost, st));
@@ -2677,8 +2645,7 @@ static int import_enqueue(rf_amd_batch* b, const std::vector<FilterOut>& outs, c
   HIPCHK(hipMemcpyAsync(b->d_pplans.p, b->pplans.data(), 16ull * F, hipMemcpyHostToDevice, st));
   {
     LaunchArgs a = make_args(b, st);
-    if (int lrc = rf_launch_plines(&a))
-      return fail(RF_AMD_EINVAL, std::string("probe-line launch: ") + hipGetErrorString((hipError_t)lrc));
+    if (int lrc = launch_rc("probe-line", rf_launch_plines(&a))) return lrc;
   }
   HIPCHK(hipStreamSynchronize(st));
   return note_built(b, st);
@@ -2744,7 +2711,7 @@ extern "C" int rf_amd_batch_export(rf_amd_batch* b, void* d_pages, uint64_t page
     so += inf[f].num_indices;
   }
   if (!d_pages || !d_slots || pages_bytes < po || num_slots < so) return fail(RF_AMD_EINVAL, "export buffers too small");
-  hipStream_t st = stream ? (hipStream_t)stream : b->eng->stream;
+  hipStream_t st = stream_of(b->eng, stream);
   po = so = 0;
   for (uint32_t f = 0; f < b->F; f++) {
     const FilterPlan& p = b->plans[f];
@@ -3133,7 +3100,7 @@ extern "C" int rf_amd_lookup_async(rf_amd_batch* b, const void* h_keys, uint32_t
   HIPCHK(hipSetDevice(b->eng->device));
   auto* s = new rf_amd_lookup_async_state();
   s->b = b;
-  s->st = stream ? (hipStream_t)stream : b->eng->stream;
+  s->st = stream_of(b->eng, stream);
   s->n = n;
   s->h_found = h_found;
   s->cb = callback;
@@ -3202,8 +3169,8 @@ extern "C" int rf_amd_hash_keys(rf_amd_engine* e, const rf_amd_config* cfg, cons
   if (int rc = check_cfg(cfg)) return rc;
   if (n && (!d_keys || !d_hashes || key_len == 0)) return fail(RF_AMD_EINVAL, "null keys / output");
   HIPCHK(hipSetDevice(e->device));
-  if (rf_launch_hash(stream ? stream : e->stream, fixed_kind(d_keys, key_len), d_keys, nullptr, key_len, cfg->seed,
-                     n, d_hashes))
+  if (rf_launch_hash(stream_of(e, stream), fixed_kind(d_keys, key_len), d_keys, nullptr, key_len, cfg->seed, n,
+                     d_hashes))
     return fail(RF_AMD_EINVAL, "hash kernel launch failed");
   return 0;
 }
@@ -3214,7 +3181,7 @@ extern "C" int rf_amd_hash_var_keys(rf_amd_engine* e, const rf_amd_config* cfg, 
   if (int rc = check_cfg(cfg)) return rc;
   if (n && (!d_bytes || !d_offsets || !d_hashes)) return fail(RF_AMD_EINVAL, "null keys / output");
   HIPCHK(hipSetDevice(e->device));
-  if (rf_launch_hash(stream ? stream : e->stream, IN_VAR, d_bytes, d_offsets, 0, cfg->seed, n, d_hashes))
+  if (rf_launch_hash(stream_of(e, stream), IN_VAR, d_bytes, d_offsets, 0, cfg->seed, n, d_hashes))
     return fail(RF_AMD_EINVAL, "hash kernel launch failed");
   return 0;
 }
@@ -3237,7 +3204,7 @@ extern "C" int rf_amd_route_probes(rf_amd_engine* e, const uint32_t* d_hashes, c
   if (!d_hashes || !d_filter_id || !d_route || !d_pairs || !d_perm || !d_scratch)
     return fail(RF_AMD_EINVAL, "null route buffer");
   HIPCHK(hipSetDevice(e->device));
-  hipStream_t st = stream ? (hipStream_t)stream : e->stream;
+  hipStream_t st = stream_of(e, stream);
   uint32_t* scratch = static_cast<uint32_t*>(d_scratch);
   const uint64_t words = rf_route_scratch_words(n, world);
   uint64_t* d_tot = reinterpret_cast<uint64_t*>(scratch + ((words + 1) & ~1ull));
@@ -3257,7 +3224,7 @@ extern "C" int rf_amd_unroute_found(rf_amd_engine* e, const uint64_t* d_back, co
   if (!e) return fail(RF_AMD_ENODEV, "no engine");
   if (n && (!d_back || !d_perm || !d_found)) return fail(RF_AMD_EINVAL, "null unroute buffer");
   HIPCHK(hipSetDevice(e->device));
-  if (rf_launch_unroute(stream ? stream : e->stream, d_back, d_perm, n, d_found))
+  if (rf_launch_unroute(stream_of(e, stream), d_back, d_perm, n, d_found))
     return fail(RF_AMD_EINVAL, "unroute kernel launch failed");
   return 0;
 }

@@ -3175,14 +3175,14 @@ extern "C" int rf_launch_estimate(void* stream, const EstFilter* fl, uint32_t nu
   if (total_idx) {
     hipLaunchKernelGGL(k_est_decode, dim3((total_idx + 3) / 4), dim3(256), 0, (hipStream_t)stream, fl, num_filters,
                        total_idx, lis, bitmap, counters);
-    if (hipGetLastError() != hipSuccess) return 1;
+    if (int rc = launch_status()) return rc;
   }
   const uint64_t n4 = bitmap_words / 4;
   const uint64_t want = (n4 + 255) / 256 + 1;
   const uint32_t grid = (uint32_t)(want < 2048 ? want : 2048);
   hipLaunchKernelGGL(k_popcount, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const uint4*)bitmap, n4,
                      counters + 1);
-  return hipGetLastError() == hipSuccess ? 0 : 1;
+  return launch_status();
 }
 
 // per-build counters zeroed in one launch (instead of one memset each)
@@ -3209,7 +3209,7 @@ extern "C" int rf_launch_build_init(void* stream, uint32_t* cb_count, uint32_t* 
   const uint32_t want = (num_cb > num_out_words ? num_cb : num_out_words) / 256 + 1;
   hipLaunchKernelGGL(k_build_init, dim3(want < 1024 ? want : 1024), dim3(256), 0, (hipStream_t)stream, cb_count,
                      cb_cursor, num_cb, outs_words, num_out_words, overflow, spill, plist);
-  return hipGetLastError() == hipSuccess ? 0 : 1;
+  return launch_status();
 }
 
 // data_key_hash over a batch (btree_pack's fingerprint loop, src/btree.c:4020-4024)
@@ -3244,7 +3244,7 @@ extern "C" int rf_launch_hash(void* stream, int kind, const void* in0, const uin
     default: L(IN_VAR); break;
   }
 #undef L
-  return hipGetLastError() == hipSuccess ? 0 : 1;
+  return launch_status();
 }
 
 // ======================================================================================
@@ -3388,7 +3388,7 @@ extern "C" int rf_launch_route(void* stream, const uint32_t* hashes, const uint3
   if (nblk)
     hipLaunchKernelGGL(k_route_scatter, dim3(nblk), dim3(ROUTE_NT), 0, st, hashes, gfid, n, route, num_g, world, off,
                        pairs, perm, err);
-  return hipGetLastError() == hipSuccess ? 0 : 1;
+  return launch_status();
 }
 
 extern "C" int rf_launch_unroute(void* stream, const uint64_t* back, const uint32_t* perm, uint64_t n,
@@ -3396,7 +3396,7 @@ extern "C" int rf_launch_unroute(void* stream, const uint64_t* back, const uint3
   if (n == 0) return 0;
   hipLaunchKernelGGL(k_unroute, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, back, perm, n,
                      found);
-  return hipGetLastError() == hipSuccess ? 0 : 1;
+  return launch_status();
 }
 
 // routing_filter_verify (src/routing_filter.c:1163-1183): keys whose found_values lacks `value`
@@ -3414,7 +3414,7 @@ extern "C" int rf_launch_count_missing(void* stream, const uint64_t* found, uint
   const uint64_t want = (n + 255) / 256;
   hipLaunchKernelGGL(k_count_missing, dim3((uint32_t)(want < 4096 ? (want ? want : 1) : 4096)), dim3(256), 0,
                      (hipStream_t)stream, found, n, value, missing);
-  return hipGetLastError() == hipSuccess ? 0 : 1;
+  return launch_status();
 }
 
 // ======================================================================================
@@ -4567,12 +4567,7 @@ __global__ __launch_bounds__(FAN_NT) void k_probe_fanout_ragged(const void* __re
       // 64 whose hash nothing uses
 #pragma unroll
       for (int u = 0; u < FAN_U; u++) {
-        const uint32_t p = p0 + (uint32_t)u * WAVE;
-        uint32_t k = 0;
-#pragma unroll
-        for (uint32_t w = WAVE / 2; w >= 1; w >>= 1)
-          if (s_off[wv][k + w] <= p) k += w;
-        hh[u] = s_h[wv][k];
+        hh[u] = s_h[wv][wave_owner_of(s_off[wv], p0 + (uint32_t)u * WAVE)];
       }
       // group heads: scalar loads through the constant address space when the whole wave names
       // one member, one plain load per lane otherwise
@@ -4655,15 +4650,8 @@ __global__ __launch_bounds__(FC_NT) void k_found_count(const uint64_t* __restric
       const uint64_t i = t0 + (uint64_t)k * FC_NT + threadIdx.x;
       if (i < m) c += (uint32_t)__popcll(found[i]);
     }
-    c = wave_incl_scan(c);
-    if ((threadIdx.x & (WAVE - 1)) == WAVE - 1) s_c[threadIdx.x / WAVE] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      uint32_t s = 0;
-      for (int w = 0; w < FC_NT / WAVE; w++) s += s_c[w];
-      cnt[t] = s;
-    }
-    __syncthreads();
+    const uint32_t s = block_sum<FC_NT>(c, s_c);
+    if (threadIdx.x == 0) cnt[t] = s;
   }
 }
 
@@ -4720,8 +4708,7 @@ extern "C" int rf_launch_found_compact(void* stream, const uint64_t* found, uint
   if (ntiles) hipLaunchKernelGGL(k_found_count, g, dim3(FC_NT), 0, st, found, m, ntiles, cnt);
   hipLaunchKernelGGL(k_found_scan, dim3(1), dim3(1024), 0, st, cnt, ntiles, off, count);
   if (ntiles && cap) hipLaunchKernelGGL(k_found_emit, g, dim3(FC_NT), 0, st, found, m, ntiles, off, cand, cap);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return launch_status();
 }
 
 // diagnostics (rf_amd_diag_fanout_max_blocks): a cap on the grid below, so that a small probe
@@ -4731,47 +4718,31 @@ extern "C" void rf_fanout_set_max_blocks(uint32_t blocks) {
   g_fanout_max_blocks.store(blocks, std::memory_order_relaxed);
 }
 
-// offs: the n + 1 byte offsets of IN_VAR keys (in0 = their bytes), unused by the other kinds
+// offs: the n + 1 byte offsets of IN_VAR keys (in0 = their bytes), unused by the other kinds.
+// moff == nullptr: the fixed form, K members per key; else the ragged form, moff = the n + 1 pair
+// offsets of the keys' member lists (K unused).
 extern "C" int rf_launch_probe_fanout(void* stream, int kind, const void* in0, const uint64_t* offs, uint32_t key_len,
                                       uint32_t seed, const ProbeGroup* groups, uint32_t ng, const uint32_t* member,
-                                      uint32_t K, uint64_t n, uint64_t* found) {
+                                      uint32_t K, const uint64_t* moff, uint64_t n, uint64_t* found) {
   if (n == 0) return 0;
   uint64_t nblk = ((n + WAVE - 1) / WAVE + FAN_NT / WAVE - 1) / (FAN_NT / WAVE);
   if (nblk > 0x7fffffffull) nblk = 0x7fffffffull;
   const uint32_t cap = g_fanout_max_blocks.load(std::memory_order_relaxed);
   if (cap && nblk > cap) nblk = cap;
   const dim3 g((uint32_t)nblk), b(FAN_NT);
-#define L(KD) hipLaunchKernelGGL((k_probe_fanout<KD>), g, b, 0, (hipStream_t)stream, in0, offs, key_len, seed, groups, ng, member, K, n, found)
+  hipStream_t st = (hipStream_t)stream;
+#define L(KD)                                                                                                      \
+  if (moff)                                                                                                        \
+    hipLaunchKernelGGL((k_probe_fanout_ragged<KD>), g, b, 0, st, in0, offs, key_len, seed, groups, ng, member, moff, n, found); \
+  else                                                                                                             \
+    hipLaunchKernelGGL((k_probe_fanout<KD>), g, b, 0, st, in0, offs, key_len, seed, groups, ng, member, K, n, found)
   switch (kind) {
     KEY_KIND_CASES(L)
     case IN_HASH: L(IN_HASH); break;
     default: return (int)hipErrorInvalidValue;
   }
 #undef L
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
-}
-
-// the ragged form: moff = the n + 1 pair offsets of the keys' member lists
-extern "C" int rf_launch_probe_fanout_ragged(void* stream, int kind, const void* in0, const uint64_t* offs,
-                                             uint32_t key_len, uint32_t seed, const ProbeGroup* groups, uint32_t ng,
-                                             const uint32_t* member, const uint64_t* moff, uint64_t n,
-                                             uint64_t* found) {
-  if (n == 0) return 0;
-  uint64_t nblk = ((n + WAVE - 1) / WAVE + FAN_NT / WAVE - 1) / (FAN_NT / WAVE);
-  if (nblk > 0x7fffffffull) nblk = 0x7fffffffull;
-  const uint32_t cap = g_fanout_max_blocks.load(std::memory_order_relaxed);
-  if (cap && nblk > cap) nblk = cap;
-  const dim3 g((uint32_t)nblk), b(FAN_NT);
-#define L(KD) hipLaunchKernelGGL((k_probe_fanout_ragged<KD>), g, b, 0, (hipStream_t)stream, in0, offs, key_len, seed, groups, ng, member, moff, n, found)
-  switch (kind) {
-    KEY_KIND_CASES(L)
-    case IN_HASH: L(IN_HASH); break;
-    default: return (int)hipErrorInvalidValue;
-  }
-#undef L
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return launch_status();
 }
 
 // ---- multi-get: member updates of a resident filter set ---------------------------------
@@ -4798,8 +4769,7 @@ extern "C" int rf_launch_set_update(void* stream, const SetUpdate* a) {
   if (a->n == 0) return 0;
   if (a->n > SET_UPD_PER_LAUNCH) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(k_set_update, dim3(1), dim3(WAVE), 0, (hipStream_t)stream, *a);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return launch_status();
 }
 
 // ---- the lookup server ---------------------------------------------------------------------
@@ -5011,22 +4981,19 @@ extern "C" int rf_launch_place(void* stream, const uint8_t* img, const uint64_t*
   if (grid == 0) return 0;
   hipLaunchKernelGGL(k_place, dim3(grid), dim3(256), 0, (hipStream_t)stream, img, slots, first_page, count,
                      num_pages, num_indices, page_size, table, addrs_per_page);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return launch_status();
 }
 
 extern "C" int rf_launch_lookup_server(void* stream, const SrvReq* ring, SrvRes* res, SrvCtl* ctl, uint64_t head,
                                        uint64_t gen, uint64_t idle_ticks, uint64_t life_ticks) {
   hipLaunchKernelGGL(k_lookup_server, dim3(1), dim3(WAVE), 0, (hipStream_t)stream, ring, res, ctl, head, gen,
                      idle_ticks, life_ticks);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return launch_status();
 }
 
 extern "C" int rf_launch_probe_small(void* stream, const SmallProbe* a) {
   hipLaunchKernelGGL(k_probe_small, dim3(1), dim3(WAVE), 0, (hipStream_t)stream, *a);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return launch_status();
 }
 
 extern "C" int rf_launch_probe_groups(void* stream, const uint32_t* in, const ProbeGroup* groups, uint32_t ng,
@@ -5035,8 +5002,7 @@ extern "C" int rf_launch_probe_groups(void* stream, const uint32_t* in, const Pr
   if (n == 0) return 0;
   hipLaunchKernelGGL(k_probe_groups, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, in, groups,
                      ng, n, found, counter, done_flag, seq);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return launch_status();
 }
 
 // ======================================================================================

@@ -54,14 +54,13 @@ int rf_launch_lookup_server(void* stream, const rf::SrvReq* ring, rf::SrvRes* re
                             uint64_t gen, uint64_t idle_ticks, uint64_t life_ticks);
 
 // ---- multi-get ----------------------------------------------------------------------------
-// offs: the n + 1 byte offsets of IN_VAR keys (in0 = their bytes), unused by the other kinds
+// offs: the n + 1 byte offsets of IN_VAR keys (in0 = their bytes), unused by the other kinds.
+// moff == nullptr: the fixed form, key i against its K members (member == nullptr: all K == ng).
+// Else the ragged form: key i against member[moff[i] .. moff[i+1]) (n + 1 pair offsets), found[p]
+// for member[p]; K unused.
 int rf_launch_probe_fanout(void* stream, int kind, const void* in0, const uint64_t* offs, uint32_t key_len,
                            uint32_t seed, const rf::ProbeGroup* groups, uint32_t ng, const uint32_t* member,
-                           uint32_t K, uint64_t n, uint64_t* found);
-// the ragged form: key i against member[moff[i] .. moff[i+1]) (n + 1 pair offsets), found[p] for member[p]
-int rf_launch_probe_fanout_ragged(void* stream, int kind, const void* in0, const uint64_t* offs, uint32_t key_len,
-                                  uint32_t seed, const rf::ProbeGroup* groups, uint32_t ng, const uint32_t* member,
-                                  const uint64_t* moff, uint64_t n, uint64_t* found);
+                           uint32_t K, const uint64_t* moff, uint64_t n, uint64_t* found);
 // k_set_update: a->n <= SET_UPD_PER_LAUNCH entries into the table a->groups, one launch
 int rf_launch_set_update(void* stream, const rf::SetUpdate* a);
 // diagnostics (rf_amd_diag_fanout_max_blocks): a cap on both fan-out grids; 0 = none

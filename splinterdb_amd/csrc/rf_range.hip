@@ -134,15 +134,8 @@ __global__ __launch_bounds__(RG_NT) void k_range_find(const uint8_t* __restrict_
         c += (uint32_t)(loff[r + 1] - loff[r]);
       }
     }
-    c = wave_incl_scan(c);
-    if ((threadIdx.x & (WAVE - 1)) == WAVE - 1) s_c[threadIdx.x / WAVE] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      uint32_t s = 0;
-      for (int w = 0; w < RG_NW; w++) s += s_c[w];
-      cnt[t] = s;
-    }
-    __syncthreads();
+    const uint32_t s = block_sum<RG_NT>(c, s_c);
+    if (threadIdx.x == 0) cnt[t] = s;
   }
 }
 
@@ -240,10 +233,7 @@ __global__ __launch_bounds__(RG_NT) void k_range_emit(const uint32_t* __restrict
       const uint64_t pfirst = base + first;
       for (uint32_t p0 = 0; p0 < np; p0 += WAVE) {
         const uint32_t p = p0 + lane;
-        uint32_t k = 0;
-#pragma unroll
-        for (uint32_t w = WAVE / 2; w >= 1; w >>= 1)
-          if (s_off[wv][k + w] <= p) k += w;
+        const uint32_t k = wave_owner_of(s_off[wv], p);
         if (p < np && pfirst + p < pair_cap) member[pfirst + p] = list[s_src[wv][k] + (p - s_off[wv][k])];
       }
       wave_sync_lds();  // the next row's offsets overwrite this one's
@@ -285,6 +275,5 @@ extern "C" int rf_launch_range_route(void* stream, int var, const uint8_t* keys,
   if (ntiles)
     hipLaunchKernelGGL(k_range_emit, g, b, 0, st, range, n, ntiles, toff, m->loff, m->list, member_off, member,
                        pair_cap);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : (int)e;
+  return launch_status();
 }
