@@ -72,6 +72,13 @@ int rf_amd_diag_lookup_server_kill(rf_amd_engine *e, int err, uint32_t gap_us);
  * see which of the two the build took */
 uint64_t rf_amd_diag_k4_bitmap_builds(void);
 
+/* how many filters of this process had their probe lines cut in the dense format (any number of
+ * buckets per line; the planner takes it for a filter whose line table outgrows one XCD's L2,
+ * RF_AMD_LINES_DENSE=1 for every filter that has a dense geometry, RF_AMD_LINES_DENSE=0 for
+ * none), counted per filter at every build and import: a test reads it before and after to see
+ * which format its filters took */
+uint64_t rf_amd_diag_dense_line_filters(void);
+
 /* how many builds of this process partitioned their keys as 16-bit in-bucket keys, the format
  * the bitmap kernel reads when the partition did not spill, instead of 32-bit entries. The host
  * decides both at once, so the two counters advance together; a build that takes the bucket

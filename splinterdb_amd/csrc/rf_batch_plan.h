@@ -51,12 +51,33 @@ inline uint32_t line_log_group(uint32_t lis, uint32_t rvs, double lam, double si
   return 0;
 }
 
+// Dense lines (rf_plan.h: LINE_DENSE) for a filter whose lines are now L_now per index: the
+// smallest L < L_now whose groups of G = ceil(IS / L) <= 64 buckets hold mean + sigma sd + 2
+// entries in the line's cap = U - G, n ~ Poisson(lam G) as above. An over-full dense line costs
+// only its tail buckets the image walk, not the whole line, so sigma is a knob of its own
+// (PlanKnobs::dense_sigma). L <= 256 keeps K6's and the probes' divisions by reciprocal exact.
+// Returns G, or 0 = no dense geometry beats the current one.
+inline uint32_t line_dense_group(uint32_t lis, uint32_t rvs, double lam, double sigma, uint32_t L_now) {
+  if (rvs > 32) return 0;
+  const uint32_t IS = 1u << lis;
+  for (uint32_t L = 1; L < L_now && L <= 256; L++) {
+    const uint32_t G = (IS + L - 1) / L;
+    if (G > 64) continue;
+    const double mean = lam * G, cap = (double)(line_unary_bits(G, rvs) - G);
+    if (mean + sigma * sqrt(mean) + 2.0 <= cap) return G;
+  }
+  return 0;
+}
+// a filter's line table against the L2 of the XCD that probes it: only a larger table has
+// anything to gain from denser lines (measured: DESIGN.md section 5)
+constexpr uint64_t LINE_DENSE_MIN_TABLE = 4ull << 20;
+
 // K6 cuts a filter's probe lines from its LDS page images when the per-page group table
 // fits: each block needs IS/G + 1 entries. Returns 0: never (k_plines cuts every line),
 // 1: always (even a page of the smallest blocks fits), 2: page by page -- K6 flags a page
 // whose blocks do not fit and k_plines cuts those pages' lines.
 inline int lines_in_assembly(uint32_t lis, uint32_t lg_line, uint32_t page_size) {
-  const uint32_t IS = 1u << lis, L = IS >> (lg_line - 1);
+  const uint32_t IS = 1u << lis, L = lines_per_index(lis, lg_line);
   const uint32_t min_block = 2 + (IS - 1) / 8 + 4 + 3;
   const uint32_t maxb = page_size / min_block + 1;
   if (maxb > ASM_MAXB || L + 1 > ASM_GT) return 0;
@@ -71,6 +92,9 @@ struct PlanKnobs {
   uint32_t layout_seg = LAYOUT_SEG_MAX;  // indices per K5 workgroup: a power of two in
                                          // [LAYOUT_SEG_MIN, LAYOUT_SEG_MAX], or 0 = never split
   double line_sigma = 3.5;       // line_log_group
+  int lines_dense = -1;          // dense lines: 0 never, 1 every filter with a dense geometry,
+                                 // -1 those whose table outgrows LINE_DENSE_MIN_TABLE
+  double dense_sigma = 2.5;      // line_dense_group
 };
 
 // the filter an incremental add starts from: filter `plan` of a batch of this process
@@ -120,6 +144,7 @@ struct BatchPlan {
   uint64_t NL = 0;             // probe lines (64 B each)
   bool plines_needed = false;  // some filter's lines come from k_plines
   uint32_t line_lmax = 0;      // max probe lines per index
+  bool lines_dense = false;    // some filter has dense lines (LINE_DENSE)
   // K5 over several workgroups per filter (layout_groups): indices per workgroup, workgroup ->
   // filter << 6 | segment (~0: none), the grid of k_layout_seg (0: no filter is split),
   // whether any filter keeps one workgroup
@@ -149,19 +174,30 @@ inline int check_config(const rf_amd_config* cfg, std::string* err) {
 }
 
 // Probe side of a filter whose num_fp, lnb, vs, num_indices and idx_base are set: remainder
-// widths, the probe-line group, and the filter's place in the batch's line table
-// (*line_total: lines of the filters before it, advanced by its own; *line_lmax raised to its
-// lines per index). The one place that derives them, for built and imported batches alike.
-inline void probe_geometry(FilterPlan& p, const rf_amd_config& cfg, double sigma, uint64_t* line_total,
-                           uint32_t* line_lmax) {
+// widths, the probe-line group (dense where the knobs and the table's size say so), and the
+// filter's place in the batch's line table (*line_total: lines of the filters before it,
+// advanced by its own; *line_lmax raised to its lines per index; *any_dense set by a dense
+// filter). The one place that derives them, for built and imported batches alike.
+// fresh: a filter built in one add or imported -- what the dense format was measured on; the
+// rounds of an incremental chain keep the current format unless the knob forces it.
+inline void probe_geometry(FilterPlan& p, const rf_amd_config& cfg, const PlanKnobs& knobs, bool fresh,
+                           uint64_t* line_total, uint32_t* line_lmax, bool* any_dense) {
   const uint32_t lis = cfg.log_index_size;
+  const double lam = (double)p.num_fp / (double)(1ull << p.lnb);
   p.rem = cfg.fingerprint_size - p.lnb;
   p.rvs = p.rem + p.vs;
-  p.lg_line = line_log_group(lis, p.rvs, (double)p.num_fp / (double)(1ull << p.lnb), sigma);
+  p.lg_line = line_log_group(lis, p.rvs, lam, knobs.line_sigma);
+  if (p.lg_line && knobs.lines_dense != 0) {
+    const uint32_t L = lines_per_index(lis, p.lg_line);
+    if (knobs.lines_dense > 0 || (fresh && (uint64_t)p.num_indices * L * 64 > LINE_DENSE_MIN_TABLE))
+      if (const uint32_t G = line_dense_group(lis, p.rvs, lam, knobs.dense_sigma, L)) p.lg_line = LINE_DENSE | (G - 1);
+  }
   p.line_base = (uint32_t)*line_total;
   if (p.lg_line) {
-    *line_total += (uint64_t)p.num_indices << (lis - (p.lg_line - 1));
-    *line_lmax = std::max(*line_lmax, (1u << lis) >> (p.lg_line - 1));
+    const uint32_t L = lines_per_index(lis, p.lg_line);
+    if (line_is_dense(p.lg_line)) *any_dense = true;
+    *line_total += (uint64_t)p.num_indices * L;
+    *line_lmax = std::max(*line_lmax, L);
   }
 }
 
@@ -394,7 +430,7 @@ inline int plan_batch(const BatchInput& in0, const PlanKnobs& knobs, BatchPlan* 
     p.idx_base = b.I;
     p.page_base = b.PS;
     p.pf_base = b.PF;
-    probe_geometry(p, cfg, knobs.line_sigma, &b.NL, &b.line_lmax);
+    probe_geometry(p, cfg, knobs, !op && !b.chained, &b.NL, &b.line_lmax, &b.lines_dense);
     const int la = p.lg_line ? lines_in_assembly(lis, p.lg_line, cfg.page_size) : 0;
     p.lines_asm = la != 0;
     p.lines_flag = la == 2;
@@ -482,7 +518,7 @@ inline int plan_import(const rf_amd_config* cfgp, uint32_t F, const rf_amd_filte
     p.page_cap = in.num_pages;
     p.page_base = (uint32_t)pages_total;
     p.idx_base = (uint32_t)idx_total;
-    probe_geometry(p, cfg, knobs.line_sigma, &b.NL, &b.line_lmax);
+    probe_geometry(p, cfg, knobs, true, &b.NL, &b.line_lmax, &b.lines_dense);
     if (p.lg_line) b.plines_needed = true;
     b.pplans[f] = pack_pplan(p);
     pages_total += in.num_pages;

@@ -360,6 +360,9 @@ struct rf_amd_batch : BatchPlan {
 // RF_AMD_LAYOUT_SEG: indices per K5 workgroup, a power of two in [256, 4096] (default 4096;
 // larger values mean 4096, 0 or anything else the one-workgroup kernel for every filter).
 // RF_AMD_LINE_SIGMA: line_log_group's margin (tuning knob, default 3.5).
+// RF_AMD_LINES_DENSE: 0 = no filter takes dense probe lines, anything else = every filter that
+// has a dense geometry does; unset = those whose line table outgrows one XCD's L2.
+// RF_AMD_DENSE_SIGMA: line_dense_group's margin (tuning knob, default 2.5).
 // RF_AMD_WIDE64, RF_AMD_OLD_DECODE, RF_AMD_OLD_RESPLIT_OFF (set at all): incremental adds keep
 // 64-bit entries / always decode old filters' images / decode them when the geometry changed.
 static PlanKnobs plan_knobs_env() {
@@ -372,10 +375,22 @@ static PlanKnobs plan_knobs_env() {
     k.layout_seg = (v < LAYOUT_SEG_MIN || (v & (v - 1))) ? 0 : v > LAYOUT_SEG_MAX ? LAYOUT_SEG_MAX : (uint32_t)v;
   }
   if (const char* e = getenv("RF_AMD_LINE_SIGMA"); e && atof(e) > 0.0) k.line_sigma = atof(e);
+  if (const char* e = getenv("RF_AMD_LINES_DENSE"); e && *e) k.lines_dense = e[0] == '0' ? 0 : 1;
+  if (const char* e = getenv("RF_AMD_DENSE_SIGMA"); e && atof(e) > 0.0) k.dense_sigma = atof(e);
   return k;
 }
 
 extern "C" const char* rf_amd_last_error(void) { return g_err.c_str(); }
+
+// filters whose probe lines were cut in the dense format, over every build and import of the
+// process (rf_amd_diag_dense_line_filters)
+static std::atomic<uint64_t> g_dense_line_filters{0};
+template <typename Batch>
+static void note_dense_lines(const Batch* b) {
+  uint64_t n = 0;
+  for (const FilterPlan& p : b->plans) n += line_is_dense(p.lg_line) ? 1 : 0;
+  if (n) g_dense_line_filters.fetch_add(n, std::memory_order_relaxed);
+}
 
 // ---- engines alive at process exit ---------------------------------------------------------
 // The compiler-generated constructor of this library registers its kernels with HIP when the
@@ -992,6 +1007,7 @@ static LaunchArgs make_args(rf_amd_batch* b, hipStream_t st) {
   a.slots = b->d_slots.as<uint64_t>();
   a.lines = b->d_lines.as<uint4>();
   a.line_lmax = b->line_lmax;
+  a.lines_dense = b->lines_dense ? 1u : 0u;
   a.plines_needed = b->plines_needed ? 1u : 0u;
   a.pg_noline = b->d_pg_noline.as<uint32_t>();
   a.idx_filter = b->d_idx_filter.as<uint32_t>();
@@ -1067,6 +1083,7 @@ static int do_build(rf_amd_batch* b, int kind, const void* in0, const uint64_t* 
     if (int rc = launch_rc("old decode", rf_launch_old_decode(&a))) return rc;
   }
   b->err_ready.store(false, std::memory_order_release);  // a rebuild: read the new bits back
+  note_dense_lines(b);
   int rc = rf_launch_build(&a);
   // counted once every kernel of the build is queued: a lookup that finds the stream idle
   // after reading this count cannot miss a build it covers
@@ -1853,6 +1870,7 @@ struct LookupClock {
 extern "C" const char* rf_amd_build_id(void) { return RF_AMD_SRC_ID; }
 
 extern "C" uint64_t rf_amd_diag_k4_bitmap_builds(void) { return rf_k4_bitmap_builds(); }
+extern "C" uint64_t rf_amd_diag_dense_line_filters(void) { return g_dense_line_filters.load(std::memory_order_relaxed); }
 extern "C" uint64_t rf_amd_diag_part16_builds(void) { return rf_part16_builds(); }
 
 extern "C" int rf_amd_diag_lookup_stats(uint64_t* out, int reset) {
@@ -2645,6 +2663,7 @@ static int import_enqueue(rf_amd_batch* b, const std::vector<FilterOut>& outs, c
   HIPCHK(hipMemcpyAsync(b->d_pplans.p, b->pplans.data(), 16ull * F, hipMemcpyHostToDevice, st));
   {
     LaunchArgs a = make_args(b, st);
+    note_dense_lines(b);
     if (int lrc = launch_rc("probe-line", rf_launch_plines(&a))) return lrc;
   }
   HIPCHK(hipStreamSynchronize(st));

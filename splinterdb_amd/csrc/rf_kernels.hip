@@ -2485,6 +2485,97 @@ __device__ __forceinline__ void assemble_atomic(const FilterPlan& P, uint32_t p,
 constexpr uint32_t ASM_RUN = 16;    // entries per thread-run in phase C
 constexpr uint32_t ASM_MAXE = 16384;  // entries per page covered by the run table
 
+// ---- probe-line geometry (rf_plan.h: lg_line) -------------------------------------------------
+// x / d for x < 4200 and a divisor d <= 256 given as its reciprocal r = rcp(d): (x + 0.5) r lies
+// at least 0.5 / d >= 2^-9 from every integer, and the reciprocal's and the product's rounding
+// move it by less than 4200 * 2^-22 < 2^-9 -- the truncation is the exact quotient.
+__device__ __forceinline__ float rcp_small(uint32_t d) { return __builtin_amdgcn_rcpf((float)d); }
+__device__ __forceinline__ uint32_t div_small(uint32_t x, float r) { return (uint32_t)(((float)x + 0.5f) * r); }
+
+// The geometry of a filter's lines from its lg_line and rvs -- every producer and consumer of
+// lines goes through this. G buckets per line, L lines per index, U unary bits; group(b) = the
+// line within its index of bucket offset b (a shift, or dense: the reciprocal of G).
+struct LineGeo {
+  uint32_t G, L, U, lgG;
+  float rG;
+  bool dense;
+  __device__ __forceinline__ uint32_t group(uint32_t b) const { return dense ? div_small(b, rG) : b >> lgG; }
+};
+// DENSE = false: the caller's batch has no dense filter, and everything dense folds away.
+template <bool DENSE>
+__device__ __forceinline__ LineGeo line_geo(uint32_t lg_line, uint32_t rvs, uint32_t lis) {
+  LineGeo g;
+  g.dense = DENSE && line_is_dense(lg_line);
+  g.lgG = g.dense ? 0u : lg_line - 1;
+  g.G = g.dense ? line_group(lg_line) : 1u << g.lgG;
+  g.rG = g.dense ? rcp_small(g.G) : 0.0f;
+  g.L = g.dense ? div_small((1u << lis) - 1u, g.rG) + 1u : (1u << lis) >> g.lgG;
+  g.U = g.dense ? line_unary_bits(g.G, rvs) : 128u;
+  return g;
+}
+// the line of bucket `bucket` (index << lis | offset) relative to its filter's first line, and
+// the bucket's place j in that line's group
+__device__ __forceinline__ void line_locate(const LineGeo& g, uint32_t bucket, uint32_t lis, uint32_t& line,
+                                            uint32_t& j) {
+  if (g.dense) {
+    const uint32_t bo = bucket & ((1u << lis) - 1u), k = div_small(bo, g.rG);
+    line = (bucket >> lis) * g.L + k;
+    j = bo - k * g.G;
+  } else {
+    line = bucket >> g.lgG;
+    j = bucket & (g.G - 1u);
+  }
+}
+
+// The two 64-bit halves of quarter qq (bits [128 qq, 128 qq + 128)) of a dense line ("probe
+// lines, dense"): the first U bits of the group's ne-bit unary code, then the first fields of
+// its n entries that fit 512 - U bits. bits64(p): 64 bits of the image from bit p; the code
+// starts at bit ecode, the group's first field at bit efield.
+template <typename Bits64>
+__device__ __forceinline__ void dense_line_quarter(Bits64 bits64, uint32_t qq, uint32_t U, uint32_t ne, uint32_t n,
+                                                   uint32_t rvs, uint32_t ecode, uint32_t efield, uint64_t (&w)[2]) {
+  const uint32_t ue = min(U, ne);                                     // unary bits kept
+  const uint32_t fe = U + (rvs ? min(n, (512u - U) / rvs) * rvs : 0u);  // end of the fields kept
+#pragma unroll
+  for (int h = 0; h < 2; h++) {
+    const uint32_t o = qq * 128 + h * 64;
+    uint64_t x = 0;
+    if (o < ue) x = bits64(ecode + o) & lowmask64(min(64u, ue - o));
+    const uint32_t lo = max(o, U), hi = min(o + 64u, fe);
+    if (lo < hi) x |= (bits64(efield + (lo - U)) & lowmask64(hi - lo)) << (lo - o);
+    w[h] = x;
+  }
+}
+
+// the same quarter of a line in the current format ("probe lines"): 128 unary bits, all ones when
+// the group's code or its fields do not fit, and the fields from bit 128
+template <typename Bits64>
+__device__ __forceinline__ void classic_line_quarter(Bits64 bits64, uint32_t qq, uint32_t ne, uint32_t n, uint32_t rvs,
+                                                     uint32_t ecode, uint32_t efield, uint64_t (&w)[2]) {
+  const bool ovf = ne > 128 || n * rvs > 384;
+#pragma unroll
+  for (int h = 0; h < 2; h++) {
+    const uint32_t o = qq * 128 + h * 64;
+    uint64_t x = 0;
+    if (ovf) {
+      x = o < 128 ? ~0ull : 0ull;
+    } else if (o < 128) {
+      const uint32_t hi = min(o + 64, ne);
+      if (o < hi) x = bits64(ecode + o) & lowmask64(hi - o);
+    } else {
+      const uint32_t ro = o - 128, hi = min(ro + 64, n * rvs);
+      if (ro < hi) x = bits64(efield + ro) & lowmask64(hi - ro);
+    }
+    w[h] = x;
+  }
+}
+template <typename Bits64>
+__device__ __forceinline__ void line_quarter(Bits64 bits64, const LineGeo& g, uint32_t qq, uint32_t ne, uint32_t n,
+                                             uint32_t rvs, uint32_t ecode, uint32_t efield, uint64_t (&w)[2]) {
+  if (g.dense) dense_line_quarter(bits64, qq, g.U, ne, n, rvs, ecode, efield, w);
+  else classic_line_quarter(bits64, qq, ne, n, rvs, ecode, efield, w);
+}
+
 // 64 bits of the LDS page image from bit `bitpos` (the image has 4 words of tail padding)
 __device__ __forceinline__ uint64_t lds_bits64(const uint32_t* s_pg, uint32_t bitpos) {
   const uint32_t w = bitpos >> 5, sh = bitpos & 31;
@@ -2500,6 +2591,7 @@ __device__ __forceinline__ uint64_t lds_bits64(const uint32_t* s_pg, uint32_t bi
 // with one atomic: adjacent lanes share at most a window edge. (D) 16-byte stores.
 // Measured before: entry-parallel single-bit atomics (~19 LDS conflict cycles per LDS
 // instruction), and a byte-serial gather per 16-byte chunk (3.6x slower again).
+template <bool DENSE>
 __global__ __launch_bounds__(ASM_NT) __attribute__((amdgpu_waves_per_eu(8))) void k_assemble(const FilterPlan* __restrict__ plans,
                                                      const uint32_t* __restrict__ pg_filter,
                                                      const uint32_t* __restrict__ idx_cnt,
@@ -2545,7 +2637,8 @@ __global__ __launch_bounds__(ASM_NT) __attribute__((amdgpu_waves_per_eu(8))) voi
   const uint32_t IS = 1u << lis, rvs = P.rvs;
   // probe lines cut from this page (phase E): line groups of G buckets, L per block; a page
   // whose group table would not fit s_gs has its lines cut by k_plines_list
-  const uint32_t lgG = P.lines_asm ? P.lg_line - 1 : 0u, G = 1u << lgG, L = IS >> lgG;
+  const LineGeo lg = line_geo<DENSE>(P.lines_asm ? P.lg_line : 1u, rvs, lis);
+  const uint32_t G = lg.G, L = lg.L;
   const bool cut = P.lines_asm && !(P.lines_flag && nb * (L + 1) > ASM_GT);
   // (A) metadata + entry offsets (2 blocks per thread)
   uint32_t cj[2], oj[2], sj[2], sum = 0;
@@ -2705,11 +2798,11 @@ __global__ __launch_bounds__(ASM_NT) __attribute__((amdgpu_waves_per_eu(8))) voi
     if (r != threadIdx.x) load_run(r, ev, pv);
     if (cut) {
       const uint32_t gb = j * (L + 1);
-      const uint32_t gp = k0 ? ((pv >> bsh) & bmask) >> lgG : 0u;  // group of the entry before the run
+      const uint32_t gp = k0 ? lg.group((pv >> bsh) & bmask) : 0u;  // group of the entry before the run
       uint32_t last = ev[0];
 #pragma unroll
       for (uint32_t i = 1; i < ASM_RUN; i++) last = i < len ? ev[i] : last;
-      const uint32_t gl = ((last >> bsh) & bmask) >> lgG;  // group of the run's last entry
+      const uint32_t gl = lg.group((last >> bsh) & bmask);  // group of the run's last entry
       // groups (gp, gl] start in this run (usually none or one), at the entry after those of
       // smaller groups: entries below hi | (gG << bsh), hi = the index bits all entries share
       const uint32_t hi = bsh + lis >= 32 ? 0u : ev[0] & ~((IS << bsh) - 1u);
@@ -2855,7 +2948,7 @@ __global__ __launch_bounds__(ASM_NT) __attribute__((amdgpu_waves_per_eu(8))) voi
     __syncthreads();
     if (it < nw) {
       const uint32_t ex = ex_all - s_wpre[j];
-      for (uint32_t k = (ex + G) >> lgG; k < L && k * G - 1 < ex + ones; k++)
+      for (uint32_t k = lg.group(ex + G); k < L && k * G - 1 < ex + ones; k++)
         s_gs[j * (L + 1) + k] = (uint16_t)(w * 64 + select64_fast(x, k * G - 1 - ex) + 1);
     }
     __syncthreads();
@@ -2864,29 +2957,18 @@ __global__ __launch_bounds__(ASM_NT) __attribute__((amdgpu_waves_per_eu(8))) voi
   DBG_PHASE_K(3, 4);
   // E2: 4 lanes per line, 16 bytes each
   const uint32_t nt = nb * L * 4;
+  const float rL = rcp_small(L);  // (dense: nb L <= ASM_GT lines per page, L <= 256)
   for (uint32_t u = threadIdx.x; u < nt; u += ASM_NT) {
-    const uint32_t j = u >> (lis - lgG + 2), rest = u & (4 * L - 1), gl = rest >> 2, qq = rest & 3;  // L = 2^(lis - lgG)
+    // the current format: L = 2^(lis - lgG) lines per block
+    const uint32_t j = lg.dense ? div_small(u >> 2, rL) : u >> (lis - lg.lgG + 2);
+    const uint32_t gl = lg.dense ? (u >> 2) - j * L : (u & (4 * L - 1)) >> 2, qq = u & 3;
     const uint32_t c = s_c[j];
     const uint32_t ebit = (s_off[j] + 2) * 8, rbit = (s_off[j] + 2 + (c + IS - 1) / 8 + 4) * 8;
     const uint32_t a = s_gs[j * (L + 1) + gl], ne2 = s_gs[j * (L + 1) + gl + 1] - a;
-    const uint32_t n = ne2 - G, E = a - gl * G;
-    const bool ovf = ne2 > 128 || n * rvs > 384;
+    // (an index's last dense group is shorter)
+    const uint32_t n = ne2 - (lg.dense ? min(G, IS - gl * G) : G), E = a - gl * G;
     uint64_t wv[2];
-#pragma unroll
-    for (int h = 0; h < 2; h++) {
-      const uint32_t o = qq * 128 + h * 64;
-      uint64_t x = 0;
-      if (ovf) {
-        x = o < 128 ? ~0ull : 0ull;
-      } else if (o < 128) {
-        const uint32_t hi = min(o + 64, ne2);
-        if (o < hi) x = lds_bits64(s_pg, ebit + a + o) & lowmask64(hi - o);
-      } else {
-        const uint32_t ro = o - 128, hi = min(ro + 64, n * rvs);
-        if (ro < hi) x = lds_bits64(s_pg, rbit + E * rvs + ro) & lowmask64(hi - ro);
-      }
-      wv[h] = x;
-    }
+    line_quarter([&](uint32_t bit) { return lds_bits64(s_pg, bit); }, lg, qq, ne2, n, rvs, ebit + a, rbit + E * rvs, wv);
     const uint64_t line = (uint64_t)P.line_base + (uint64_t)(b0 + j) * L + gl;
     lines[line * 4 + qq] = make_uint4((uint32_t)wv[0], (uint32_t)(wv[0] >> 32), (uint32_t)wv[1], (uint32_t)(wv[1] >> 32));
   }
@@ -3514,13 +3596,15 @@ __device__ __forceinline__ uint64_t bits64_at(const uint8_t* pg, uint64_t bitpos
 // One index's probe lines, cut by one wave from its block in the image: the block (at most
 // one page) is first copied into the wave's LDS slice `blk` with coalesced 16-byte loads;
 // both phases then read their bits from LDS. s_a: the wave's group-start table (L + 1).
+template <bool DENSE>
 __device__ __forceinline__ void plines_index(const FilterPlan& P, uint32_t g, const uint64_t* __restrict__ slots,
                                              const uint8_t* __restrict__ pages, uint4* __restrict__ lines,
                                              uint8_t* blk, uint32_t* s_a, uint32_t lane, uint32_t lis,
                                              uint32_t page_size) {
   constexpr uint32_t SLICE = MAX_PAGE + 64;
   const uint32_t IS = 1u << lis;
-  const uint32_t lgG = P.lg_line - 1, G = 1u << lgG, L = IS >> lgG;
+  const LineGeo lg = line_geo<DENSE>(P.lg_line, P.rvs, lis);
+  const uint32_t G = lg.G, L = lg.L;
   const uint8_t* pg = blk;
   const uint8_t* gp = pages + (uint64_t)P.page_base * page_size;
   const uint64_t rel_g = slots[g];
@@ -3551,7 +3635,7 @@ __device__ __forceinline__ void plines_index(const FilterPlan& P, uint32_t g, co
       const uint32_t ones = __popcll(x);
       const uint32_t ex = wave_incl_scan(ones) - ones + ones_before;
       // terminators t = kG - 1 (k = 1..L-1) inside [ex, ex + ones): group k starts after t
-      for (uint32_t k = (ex + G) >> lgG; k < L && k * G - 1 < ex + ones; k++)
+      for (uint32_t k = lg.group(ex + G); k < L && k * G - 1 < ex + ones; k++)
         s_a[k] = b0 + select64_fast(x, k * G - 1 - ex) + 1;
       ones_before = __shfl(ex + ones, WAVE - 1, WAVE);
     }
@@ -3567,24 +3651,11 @@ __device__ __forceinline__ void plines_index(const FilterPlan& P, uint32_t g, co
   for (uint32_t u = lane; u < 4 * L; u += WAVE) {
     const uint32_t gl = u >> 2, qq = u & 3;
     const uint32_t a = s_a[gl], ne = s_a[gl + 1] - a;  // encoding bits of the group = n + G
-    const uint32_t n = ne - G, E = a - gl * G;         // entries, first entry of the group
-    const bool ovf = ne > 128 || (uint64_t)n * rvs > 384;
+    // entries, first entry of the group (an index's last dense group is shorter)
+    const uint32_t n = ne - (lg.dense ? min(G, IS - gl * G) : G), E = a - gl * G;
     uint64_t w[2];
-#pragma unroll
-    for (int h = 0; h < 2; h++) {
-      const uint32_t o = qq * 128 + h * 64;
-      uint64_t x = 0;
-      if (ovf) {
-        x = o < 128 ? ~0ull : 0ull;
-      } else if (o < 128) {
-        const uint32_t hi = min(o + 64, ne);
-        if (o < hi) x = bits64_at(pg, ebit + a + o) & lowmask64(hi - o);
-      } else {
-        const uint32_t ro = o - 128, hi = min(ro + 64, n * rvs);
-        if (ro < hi) x = bits64_at(pg, rbit0 + (uint64_t)E * rvs + ro) & lowmask64(hi - ro);
-      }
-      w[h] = x;
-    }
+    line_quarter([&](uint32_t bit) { return bits64_at(pg, bit); }, lg, qq, ne, n, rvs, (uint32_t)ebit + a,
+                 (uint32_t)rbit0 + E * rvs, w);
     lines[(line0 + gl) * 4 + qq] =
         make_uint4((uint32_t)w[0], (uint32_t)(w[0] >> 32), (uint32_t)w[1], (uint32_t)(w[1] >> 32));
   }
@@ -3593,6 +3664,7 @@ __device__ __forceinline__ void plines_index(const FilterPlan& P, uint32_t g, co
 
 // Probe lines K6 did not cut, per index (rf_amd_batch_import's images and the diagnostics
 // rebuild, force = 1: every filter): one wave per index.
+template <bool DENSE>
 __global__ __launch_bounds__(256) void k_plines(const FilterPlan* __restrict__ plans,
                                                 const uint32_t* __restrict__ idx_filter,
                                                 const uint64_t* __restrict__ slots,
@@ -3611,13 +3683,14 @@ __global__ __launch_bounds__(256) void k_plines(const FilterPlan* __restrict__ p
   const FilterPlan& P = plans[f];
   if (P.lg_line == 0 || (outs && outs[f].error) || g - P.idx_base >= P.num_indices) return;
   if (!force && P.lines_asm) return;  // K6 cuts (or lists) this filter's lines
-  plines_index(P, g, slots, pages, lines, s_blk[wv], s_dyn + wv * (lmax + 1), lane, lis, page_size);
+  plines_index<DENSE>(P, g, slots, pages, lines, s_blk[wv], s_dyn + wv * (lmax + 1), lane, lis, page_size);
 }
 
 // Builds: the pages whose lines K6 left (filters it never cuts, and pages whose group table
 // does not fit its LDS) are listed by K6 in plist (plist[0] = count, then page slots); a small
 // grid walks the list, one wave per index of a listed page. An empty list costs one load per
 // workgroup (a grid over every index of the batch cost a compaction round 0.18 ms).
+template <bool DENSE>
 __global__ __launch_bounds__(256) void k_plines_list(const FilterPlan* __restrict__ plans,
                                                      const uint32_t* __restrict__ pg_filter,
                                                      const uint32_t* __restrict__ page_first,
@@ -3637,7 +3710,7 @@ __global__ __launch_bounds__(256) void k_plines_list(const FilterPlan* __restric
     const uint32_t* pf = page_first + P.pf_base;
     const uint32_t p = slot - P.page_base, b1 = pf[p + 1];
     for (uint32_t b = pf[p] + wv; b < b1; b += 256 / WAVE)
-      plines_index(P, P.idx_base + b, slots, pages, lines, s_blk[wv], s_dyn + wv * (lmax + 1), lane, lis,
+      plines_index<DENSE>(P, P.idx_base + b, slots, pages, lines, s_blk[wv], s_dyn + wv * (lmax + 1), lane, lis,
                    page_size);
   }
 }
@@ -3762,6 +3835,80 @@ __device__ __forceinline__ bool line_decode_w(const v4u& E, Win win, uint32_t j,
   return true;
 }
 
+// bit 0 of every rvs-bit field of a 64-bit word, as a table in constant memory (a scalar load
+// where rvs is wave-uniform)
+struct FieldOnes {
+  uint64_t v[33];
+  constexpr FieldOnes() : v() {
+    for (uint32_t r = 1; r <= 32; r++) {
+      uint64_t L = 0;
+      for (uint32_t k = 0; k < 64; k += r) L |= 1ull << k;
+      v[r] = L;
+    }
+  }
+};
+__constant__ FieldOnes c_field_ones = FieldOnes();
+
+// ---- probe lines, dense ----------------------------------------------------------------------
+// The format of a filter whose lg_line has LINE_DENSE set (the planner's choice: probe_geometry):
+// a line serves any G <= 64 buckets, an index has L = ceil(IS / G) lines (its last group is
+// shorter) and the filter's line idx L + g holds group g of index idx:
+//   bits [0,U)     the first U bits of the group's unary code (n + its buckets), zero padded
+//   bits [U,512)   the first floor((512 - U) / rvs) of its n fields, rvs bits each
+// with U = line_unary_bits(G, rvs) <= 160: both regions fill at the same entry count. There is no
+// overflow marker: an over-full group loses its tail, and a probe walks the image only when its
+// own bucket's terminator lies past bit U or its fields past bit 512.
+// dw(i): dword i of the line (i < 18; dwords past the line hold anything, i is not always a
+// constant). False: walk the image
+// (cut off, or the bucket's fields do not fit one 64-bit compare).
+template <typename Dw>
+__device__ __forceinline__ bool line_decode_d(Dw dw, uint32_t U, uint32_t j, uint32_t remainder, uint32_t vs,
+                                              uint32_t rvs, uint64_t& found) {
+  // the unary region's dwords, cut at bit U (plain values: no array the compiler could index)
+  auto cut = [&](uint32_t k) -> uint32_t {
+    return U >= 32 * k + 32 ? dw(k) : (U > 32 * k ? dw(k) & ((1u << (U - 32 * k)) - 1u) : 0u);
+  };
+  uint32_t p1 = 0;  // the first bit after terminator j - 1
+  if (j) {
+    const uint32_t d0 = cut(0), d1 = cut(1), d2 = cut(2), d3 = cut(3), d4 = cut(4);
+    const uint32_t r = j - 1, c0 = __popc(d0), c1 = c0 + __popc(d1), c2 = c1 + __popc(d2), c3 = c2 + __popc(d3);
+    if (r >= c3 + __popc(d4)) return false;
+    const uint32_t x = r >= c3 ? d4 : (r >= c2 ? d3 : (r >= c1 ? d2 : (r >= c0 ? d1 : d0)));
+    const uint32_t base = r >= c3 ? 128u : (r >= c2 ? 96u : (r >= c1 ? 64u : (r >= c0 ? 32u : 0u)));
+    const uint32_t before = r >= c3 ? c3 : (r >= c2 ? c2 : (r >= c1 ? c1 : (r >= c0 ? c0 : 0u)));
+    p1 = base + select32(x, r - before) + 1;
+  }
+  // the unary bits [p1, U), 64 at the most: terminator j among them, or the bucket is cut off
+  // (or holds 64 entries); p1 <= U <= 160, so the window's dwords lie inside the line
+  const uint32_t wi = p1 >> 5, sh = p1 & 31;
+  const uint32_t a0 = dw(wi), a1 = dw(wi + 1), a2 = dw(wi + 2);
+  const uint64_t y = ((uint64_t)__builtin_amdgcn_alignbit(a2, a1, sh) << 32 | __builtin_amdgcn_alignbit(a1, a0, sh)) &
+                     lowmask64(U - p1);
+  if (y == 0) return false;
+  const uint32_t c = (uint32_t)__builtin_ctzll(y);
+  found = 0;
+  if (c == 0) return true;
+  if (rvs == 0) {  // every entry is the (empty) remainder with value 0
+    found = 1;
+    return true;
+  }
+  const uint32_t b = U + (p1 - j) * rvs, nb = c * rvs, fi = b >> 5, off = b & 31;
+  if (b + nb > 512 || nb > 64) return false;
+  const uint32_t w0 = dw(fi), w1 = dw(fi + 1), w2 = dw(fi + 2);
+  const uint64_t W = (uint64_t)__builtin_amdgcn_alignbit(w2, w1, off) << 32 | __builtin_amdgcn_alignbit(w1, w0, off);
+  const uint64_t L = c_field_ones.v[rvs];
+  const uint64_t valid = nb == 64 ? ~0ull : (1ull << nb) - 1;
+  const uint64_t H = L << (rvs - 1);  // the top bit of every field
+  uint64_t Z = H & valid;             // rvs == vs: no remainder bits, every entry matches
+  if (rvs > vs) {
+    const uint64_t M = (L << rvs) - (L << vs), MH = M & ~H;
+    const uint64_t Y = (W ^ ((uint64_t)(remainder << vs) * L)) & M;
+    Z = H & valid & ~(((Y & MH) + MH) | Y);
+  }
+  found = emit_matches(Z, W, rvs, vs);
+  return true;
+}
+
 // the window from the line held in registers (Q[1..3]: the 384-bit remainder area): 96 bits at
 // dword wi (wi <= 9) -- pick the 4-dword group g = wi / 4, then dwords o..o+2 (o = wi % 4) of
 // that group's 6-dword span (21 selects instead of 36)
@@ -3859,14 +4006,24 @@ __device__ __forceinline__ void split_fp(uint32_t h, uint32_t fp_size, uint32_t 
 // whole wave probes one filter, k_probe passes P as wave-uniform values, so everything
 // derived from the plan alone (widths, masks, the SWAR field pattern) is computed once per
 // wave in scalar registers.
+template <bool DENSE>
 __device__ __forceinline__ bool probe_line(const uint4 P, uint32_t h, const uint4* __restrict__ lines,
-                                           uint32_t fp_size, uint64_t& r) {
+                                           uint32_t fp_size, uint32_t lis, uint64_t& r) {
   const uint32_t vs = P.x & 0xff, rem = (P.x >> 8) & 0xff, rvs = (P.x >> 16) & 0xff, lgl = P.x >> 24;
   r = 0;
   if (P.w) return true;  // unknown filter, or its build failed: nothing found
   if (!lgl) return false;
   uint32_t bucket, remainder;
   split_fp(h, fp_size, rem, bucket, remainder);
+  if (DENSE && line_is_dense(lgl)) {
+    // dense lines, off the fast path: the decode reads its dwords from memory as it needs them
+    // (the unary dwords, then the bucket's window of the same 64-byte line)
+    const LineGeo g = line_geo<true>(lgl, rvs, lis);
+    uint32_t line, j;
+    line_locate(g, bucket, lis, line, j);
+    const uint32_t* lw = reinterpret_cast<const uint32_t*>(lines + ((uint64_t)P.y + line) * 4);
+    return line_decode_d([&](uint32_t i) { return lw[i & 15u]; }, g.U, j, remainder, vs, rvs, r);
+  }
   const v4u* lp = reinterpret_cast<const v4u*>(lines + ((uint64_t)P.y + (bucket >> (lgl - 1))) * 4);
   v4u Q[4];
 #pragma unroll
@@ -3894,17 +4051,6 @@ __device__ __forceinline__ uint64_t probe_walk(const uint4 P, uint32_t h, uint32
 // loading its quarter t), so each probe reads its encoding with one ds_read_b128 and its remainder
 // window with three ds_read_b32 off one address. The SWAR field pattern comes from a table in
 // constant memory (one scalar load) instead of being built per wave.
-struct FieldOnes {
-  uint64_t v[33];
-  constexpr FieldOnes() : v() {
-    for (uint32_t r = 1; r <= 32; r++) {
-      uint64_t L = 0;
-      for (uint32_t k = 0; k < 64; k += r) L |= 1ull << k;
-      v[r] = L;
-    }
-  }
-};
-__constant__ FieldOnes c_field_ones = FieldOnes();
 
 // uniform 32-bit loads through the constant address space: always scalar (SMEM) loads
 __device__ __forceinline__ uint32_t sload32(const void* p) {
@@ -4014,7 +4160,7 @@ __device__ __forceinline__ void quad_gather(const uint8_t* fb, uint32_t lo, uint
 // Sweep 0.. of a full wave of one filter: hash (24-byte keys staged through LDS by LDS-DMA, or
 // hashes), gather each probe's 64-B line (quad-cooperative LDS-DMA), decode, one coalesced
 // store. False when the wave is not fast-path material (the caller takes the general path).
-template <int KIND>
+template <int KIND, bool DENSE>
 __device__ __forceinline__ bool probe_fast(const uint4* __restrict__ pplans, const FilterPlan* __restrict__ plans,
                                            const uint8_t* __restrict__ pages, const uint64_t* __restrict__ slots,
                                            const uint4* __restrict__ lines, const void* __restrict__ in0,
@@ -4047,26 +4193,34 @@ __device__ __forceinline__ bool probe_fast(const uint4* __restrict__ pplans, con
     wave_sync_lds();
     h = keys24_hash_lds(sw, lane, seed);
   }
-  const uint32_t lgG = lgl - 1;
+  const LineGeo g = line_geo<DENSE>(lgl, rvs, lis);  // wave-uniform
   // rem is in [1, 32) here: split_fp without its guards
   const uint32_t fp = h >> (32 - fp_size);
   const uint32_t bucket = fp >> rem;
   const uint32_t remainder = fp & ((1u << rem) - 1);
   const uint8_t* fb = reinterpret_cast<const uint8_t*>(lines) + ((uint64_t)U.y << 6);  // the filter's lines
   uint8_t* sb = reinterpret_cast<uint8_t*>(sw);
-  quad_gather<FAST_KSTRIDE, false>(fb, (bucket >> lgG) << 6, lane & 3, sb);
+  uint32_t line, j;
+  line_locate(g, bucket, lis, line, j);
+  quad_gather<FAST_KSTRIDE, false>(fb, line << 6, lane & 3, sb);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   wave_sync_lds();
   const uint32_t* Lw = reinterpret_cast<const uint32_t*>(sb + (lane & 3) * FAST_KSTRIDE + (lane >> 2) * 64);
-  const uint64_t L = sload64(&c_field_ones.v[rvs]);
   uint64_t r;
-  if (!line_decode_u(Lw, bucket & ((1u << lgG) - 1), remainder, vs, rvs, L, r))
+  bool ok;
+  if (g.dense) {
+    ok = line_decode_d([&](uint32_t i) { return Lw[i]; }, g.U, j, remainder, vs, rvs, r);
+  } else {
+    const uint64_t L = sload64(&c_field_ones.v[rvs]);
+    ok = line_decode_u(Lw, j, remainder, vs, rvs, L, r);
+  }
+  if (!ok)
     r = probe_walk(U, h, fs, plans, pages, slots, fp_size, lis, page_size);
   __builtin_nontemporal_store(r, found + wf + lane);
   return true;
 }
 
-template <int KIND>
+template <int KIND, bool DENSE>
 __global__ __launch_bounds__(probe_nt(KIND)) void k_probe(const uint4* __restrict__ pplans,
                                                     const FilterPlan* __restrict__ plans,
                                                     const uint8_t* __restrict__ pages,
@@ -4098,7 +4252,7 @@ __global__ __launch_bounds__(probe_nt(KIND)) void k_probe(const uint4* __restric
     if (runs) {
       const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x) / WAVE;
       const uint64_t wfs = (uint64_t)xcd_chunk(blockIdx.x, gridDim.x) * NT + wv * WAVE;  // = wf, in SGPRs
-      if (wfs < n && probe_fast<KIND>(pplans, plans, pages, slots, lines, in0, wave_tab, n, found, fp_size, seed,
+      if (wfs < n && probe_fast<KIND, DENSE>(pplans, plans, pages, slots, lines, in0, wave_tab, n, found, fp_size, seed,
                                       lis, page_size, num_filters, wfs, s_wbuf[wv]))
         return;
     }
@@ -4174,7 +4328,10 @@ __global__ __launch_bounds__(probe_nt(KIND)) void k_probe(const uint4* __restric
       // the filter's line table (uniform) and this probe's line within it as a 32-bit byte
       // offset: each load is a scalar base plus one VGPR offset (no per-load 64-bit math)
       const uint8_t* fb = reinterpret_cast<const uint8_t*>(lines) + ((uint64_t)U.y << 6);
-      const uint32_t lo = (bucket >> (lgl - 1)) << 6;
+      const LineGeo g = line_geo<DENSE>(lgl, rvs, lis);
+      uint32_t line, j;
+      line_locate(g, bucket, lis, line, j);
+      const uint32_t lo = line << 6;
       v4u* sw;
       if constexpr (WAVE_VAR) sw = reinterpret_cast<v4u*>(s_vk[threadIdx.x / WAVE]);
       else sw = s_wbuf[threadIdx.x / WAVE];
@@ -4196,7 +4353,13 @@ __global__ __launch_bounds__(probe_nt(KIND)) void k_probe(const uint4* __restric
         w2 = dw(6 + wi);
       };
       uint64_t r;
-      if (!line_decode_w(E, win, bucket & ((1u << (lgl - 1)) - 1), remainder, vs, rvs, r))
+      bool ok;
+      if (g.dense)
+        ok = line_decode_d([&](uint32_t d) { d &= 15u; return L32[(((d >> 2) - lane) & 3u) * 4 + (d & 3u)]; }, g.U, j,
+                           remainder, vs, rvs, r);
+      else
+        ok = line_decode_w(E, win, j, remainder, vs, rvs, r);
+      if (!ok)
         r = probe_walk(U, h, fs, plans, pages, slots, fp_size, lis, page_size);
       __builtin_nontemporal_store(r, found + i0);
       return;
@@ -4209,9 +4372,9 @@ __global__ __launch_bounds__(probe_nt(KIND)) void k_probe(const uint4* __restric
   if (uniform) {  // plan fields in scalar registers: the decode's masks are computed once per wave
     const uint4 U = make_uint4(__builtin_amdgcn_readfirstlane(pp.x), __builtin_amdgcn_readfirstlane(pp.y),
                                __builtin_amdgcn_readfirstlane(pp.z), __builtin_amdgcn_readfirstlane(pp.w));
-    ok = probe_line(U, h, lines, fp_size, r);
+    ok = probe_line<DENSE>(U, h, lines, fp_size, lis, r);
   } else {
-    ok = probe_line(pp, h, lines, fp_size, r);
+    ok = probe_line<DENSE>(pp, h, lines, fp_size, lis, r);
   }
   if (!ok) r = probe_walk(pp, h, fid, plans, pages, slots, fp_size, lis, page_size);
   __builtin_nontemporal_store(r, found + i0);
@@ -4223,13 +4386,13 @@ __global__ __launch_bounds__(probe_nt(KIND)) void k_probe(const uint4* __restric
 // filter into the same LDS slots, the same coalesced 8-byte store -- but the line comes from a
 // multiply-xorshift of the key words instead of XXH32, and the stored word is an XOR of the
 // line's quarter instead of its decode. Waves that are not fast-path material store 0.
-template <int KIND>
+template <int KIND, bool DENSE>
 __global__ __launch_bounds__(probe_nt(KIND)) void k_probe_floor(const uint4* __restrict__ pplans,
                                                           const uint4* __restrict__ lines,
                                                           const void* __restrict__ in0,
                                                           const uint32_t* __restrict__ wave_tab, uint64_t n,
                                                           uint64_t* __restrict__ found, uint32_t fp_size,
-                                                          uint32_t nf) {
+                                                          uint32_t lis, uint32_t nf) {
   constexpr int NT = probe_nt(KIND);
   __shared__ v4u s_wbuf[NT / WAVE][FAST_WBUF];
   const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x) / WAVE;
@@ -4246,11 +4409,12 @@ __global__ __launch_bounds__(probe_nt(KIND)) void k_probe_floor(const uint4* __r
   }
   const uint32_t t = sload32(wave_tab + wf / WAVE);
   const uint32_t fs = t >> 7;
-  uint32_t lgl = 0, rem = 0, base = 0;
+  uint32_t lgl = 0, rem = 0, rvs = 0, base = 0;
   if ((t & 127u) == WAVE && fs < nf && full) {
     const uint32_t x = sload32(&pplans[fs].x);
     lgl = x >> 24;
     rem = (x >> 8) & 0xff;
+    rvs = (x >> 16) & 0xff;
     base = sload32(&pplans[fs].y);
   }
   if (!lgl || rem == 0 || rem >= 32) {
@@ -4270,7 +4434,9 @@ __global__ __launch_bounds__(probe_nt(KIND)) void k_probe_floor(const uint4* __r
   const uint32_t bucket = (h >> (32 - fp_size)) >> rem;
   const uint8_t* fb = reinterpret_cast<const uint8_t*>(lines) + ((uint64_t)base << 6);
   uint8_t* sb = reinterpret_cast<uint8_t*>(sw);
-  quad_gather<FAST_KSTRIDE, false>(fb, (bucket >> (lgl - 1)) << 6, lane & 3, sb);
+  uint32_t line, j;  // the same table geometry as the probe's
+  line_locate(line_geo<DENSE>(lgl, rvs, lis), bucket, lis, line, j);
+  quad_gather<FAST_KSTRIDE, false>(fb, line << 6, lane & 3, sb);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   wave_sync_lds();
   const v4u E = *reinterpret_cast<const v4u*>(sb + (lane & 3) * FAST_KSTRIDE + (lane >> 2) * 64);
@@ -4283,7 +4449,7 @@ __device__ __forceinline__ uint64_t probe_group(const ProbeGroup& G, uint32_t h)
   const uint32_t fp_size = G.fpl & 0xff, lis = (G.fpl >> 8) & 0xff;
   const uint4 P = make_uint4(G.x, 0u, 0u, G.err);
   uint64_t r = 0;
-  if (!probe_line(P, h, G.lines, fp_size, r)) {  // overflowed line / no lines: walk the image
+  if (!probe_line<true>(P, h, G.lines, fp_size, lis, r)) {  // overflowed line / no lines: walk the image
     const uint32_t vs = G.x & 0xff, rem = (G.x >> 8) & 0xff, rvs = (G.x >> 16) & 0xff;
     uint32_t bucket, remainder;
     split_fp(h, fp_size, rem, bucket, remainder);
@@ -4371,6 +4537,9 @@ constexpr int FAN_NT = 256;
 #define RF_FAN_U 2
 #endif
 constexpr int FAN_U = RF_FAN_U;  // steps whose loads are in flight together
+// Both kernels are held to the 5 waves per SIMD they ran at before probe_group learnt the dense
+// line format: its branch (taken only by dense members) had cost 4 VGPRs, and two instantiations
+// a wave (profiles/dense_lines_resources.txt).
 #ifndef RF_FAN_VCAP
 #define RF_FAN_VCAP 4096
 #endif
@@ -4419,7 +4588,7 @@ __device__ __forceinline__ uint32_t fan_hash_chunk(const void* __restrict__ in0,
 }
 
 template <int KIND>
-__global__ __launch_bounds__(FAN_NT) void k_probe_fanout(const void* __restrict__ in0,
+__global__ __launch_bounds__(FAN_NT) __attribute__((amdgpu_waves_per_eu(5))) void k_probe_fanout(const void* __restrict__ in0,
                                                          const uint64_t* __restrict__ offs, uint32_t key_len,
                                                          uint32_t seed, const ProbeGroup* __restrict__ groups,
                                                          uint32_t ng, const uint32_t* __restrict__ member,
@@ -4482,7 +4651,8 @@ __global__ __launch_bounds__(FAN_NT) void k_probe_fanout(const void* __restrict_
           pf[u] = G->fpl;
           pl[u] = (uint64_t)(uintptr_t)G->lines;
         }
-        st[u] = err ? 0u : ((px[u] >> 24) ? 1u : 2u);  // 0 nothing found, 1 probe line, 2 no lines: walk
+        // 0 nothing found, 1 probe line, 2 no lines or dense lines: probe_group
+        st[u] = err ? 0u : ((px[u] >> 24) - 1u < LINE_DENSE - 1u ? 1u : 2u);
       }
       // probe lines (probe_line's addressing)
 #pragma unroll
@@ -4526,7 +4696,7 @@ __global__ __launch_bounds__(FAN_NT) void k_probe_fanout(const void* __restrict_
 // pair count, so the search never names them. From the member id on the path is
 // k_probe_fanout's. A wave whose keys own no pairs reads its two end offsets and nothing else.
 template <int KIND>
-__global__ __launch_bounds__(FAN_NT) void k_probe_fanout_ragged(const void* __restrict__ in0,
+__global__ __launch_bounds__(FAN_NT) __attribute__((amdgpu_waves_per_eu(5))) void k_probe_fanout_ragged(const void* __restrict__ in0,
                                                                 const uint64_t* __restrict__ offs,
                                                                 uint32_t key_len, uint32_t seed,
                                                                 const ProbeGroup* __restrict__ groups, uint32_t ng,
@@ -4594,7 +4764,8 @@ __global__ __launch_bounds__(FAN_NT) void k_probe_fanout_ragged(const void* __re
           pf[u] = G->fpl;
           pl[u] = (uint64_t)(uintptr_t)G->lines;
         }
-        st[u] = err ? 0u : ((px[u] >> 24) ? 1u : 2u);  // 0 nothing found, 1 probe line, 2 no lines: walk
+        // 0 nothing found, 1 probe line, 2 no lines or dense lines: probe_group
+        st[u] = err ? 0u : ((px[u] >> 24) - 1u < LINE_DENSE - 1u ? 1u : 2u);
       }
       // probe lines (probe_line's addressing)
 #pragma unroll
@@ -5112,8 +5283,9 @@ static int launch_plines_list(const LaunchArgs& a) {
   if (!a.line_lmax || !a.num_page_slots) return 0;
   const size_t lds = 4ull * (256 / WAVE) * (a.line_lmax + 1);
   const uint32_t grid = a.num_page_slots < 1024 ? a.num_page_slots : 1024;
-  hipLaunchKernelGGL(k_plines_list, dim3(grid), dim3(256), lds, (hipStream_t)a.stream, a.plans, a.pg_filter,
-                     a.page_first, a.slots, a.pages, a.pg_noline, a.lines, a.line_lmax, a.lis, a.page_size);
+  hipLaunchKernelGGL(a.lines_dense ? k_plines_list<true> : k_plines_list<false>, dim3(grid), dim3(256), lds,
+                     (hipStream_t)a.stream, a.plans, a.pg_filter, a.page_first, a.slots, a.pages, a.pg_noline, a.lines,
+                     a.line_lmax, a.lis, a.page_size);
   CHECK_LAUNCH();
   return 0;
 }
@@ -5237,9 +5409,9 @@ static int launch_build_t(const LaunchArgs& a) {
     CHECK_LAUNCH();
   }
   REC(EV_B_LAYOUT);
-  hipLaunchKernelGGL(k_assemble, dim3(a.num_page_slots), dim3(ASM_NT), 0, (hipStream_t)a.stream, a.plans, a.pg_filter,
-                     a.idx_cnt, a.idx_start, a.sorted32, a.slots, a.page_first, a.outs, a.pages, a.lines,
-                     a.pg_noline, a.lis, a.page_size);
+  hipLaunchKernelGGL(a.lines_dense ? k_assemble<true> : k_assemble<false>, dim3(a.num_page_slots), dim3(ASM_NT), 0,
+                     (hipStream_t)a.stream, a.plans, a.pg_filter, a.idx_cnt, a.idx_start, a.sorted32, a.slots,
+                     a.page_first, a.outs, a.pages, a.lines, a.pg_noline, a.lis, a.page_size);
   CHECK_LAUNCH();
   if (a.plines_needed)
     if (int rc = launch_plines_list(a)) return rc;
@@ -5255,9 +5427,9 @@ extern "C" int rf_launch_plines(const LaunchArgs* pa) {
   const LaunchArgs& a = *pa;
   if (!a.line_lmax) return 0;  // no filter of the batch has lines
   const size_t lds = 4ull * (256 / WAVE) * (a.line_lmax + 1);
-  hipLaunchKernelGGL(k_plines, dim3((a.num_idx + 3) / 4), dim3(256), lds, (hipStream_t)a.stream, a.plans,
-                     a.idx_filter, a.slots, a.pages, a.outs, a.lines, a.num_idx, a.line_lmax, a.lis,
-                     a.page_size, a.plines_force);
+  hipLaunchKernelGGL(a.lines_dense ? k_plines<true> : k_plines<false>, dim3((a.num_idx + 3) / 4), dim3(256), lds,
+                     (hipStream_t)a.stream, a.plans, a.idx_filter, a.slots, a.pages, a.outs, a.lines, a.num_idx,
+                     a.line_lmax, a.lis, a.page_size, a.plines_force);
   CHECK_LAUNCH();
   return 0;
 }
@@ -5318,12 +5490,11 @@ extern "C" int rf_launch_probe_floor(const LaunchArgs* pa, int kind, const void*
   if (!a.wave_tab || (kind != IN_KEYS24 && kind != IN_HASH)) return (int)hipErrorInvalidValue;
   const int nt = probe_nt(kind);
   dim3 g((uint32_t)((n + nt - 1) / nt)), b(nt);
-  if (kind == IN_KEYS24)
-    hipLaunchKernelGGL((k_probe_floor<IN_KEYS24>), g, b, 0, (hipStream_t)a.stream, a.pplans, a.lines, in0, a.wave_tab, n,
-                       found, a.fp_size, a.num_filters);
-  else
-    hipLaunchKernelGGL((k_probe_floor<IN_HASH>), g, b, 0, (hipStream_t)a.stream, a.pplans, a.lines, in0, a.wave_tab, n,
-                       found, a.fp_size, a.num_filters);
+  // (a batch without a dense filter runs the instantiations with everything dense compiled out)
+  auto kern = kind == IN_KEYS24 ? (a.lines_dense ? k_probe_floor<IN_KEYS24, true> : k_probe_floor<IN_KEYS24, false>)
+                                : (a.lines_dense ? k_probe_floor<IN_HASH, true> : k_probe_floor<IN_HASH, false>);
+  hipLaunchKernelGGL(kern, g, b, 0, (hipStream_t)a.stream, a.pplans, a.lines, in0, a.wave_tab, n, found, a.fp_size,
+                     a.lis, a.num_filters);
   CHECK_LAUNCH();
   return 0;
 }
@@ -5335,7 +5506,10 @@ extern "C" int rf_launch_probe(const LaunchArgs* pa, int kind, const void* in0, 
   const int nt = probe_nt(kind);
   dim3 g((uint32_t)((n + nt - 1) / nt)), b(nt);
   REC(EV_P_START);
-#define PK(K) hipLaunchKernelGGL((k_probe<K>), g, b, 0, (hipStream_t)a.stream, a.pplans, a.plans, a.pages, a.slots, a.lines, in0, offs, key_len, filter_id, a.probe_runs, a.wave_tab, n, found, a.fp_size, a.seed, a.lis, a.page_size, a.num_filters)
+#define PK(K)                                                                                                      \
+  hipLaunchKernelGGL((a.lines_dense ? k_probe<K, true> : k_probe<K, false>), g, b, 0, (hipStream_t)a.stream,        \
+                     a.pplans, a.plans, a.pages, a.slots, a.lines, in0, offs, key_len, filter_id, a.probe_runs,      \
+                     a.wave_tab, n, found, a.fp_size, a.seed, a.lis, a.page_size, a.num_filters)
   // 8 waves/SIMD: the line probe is bound by outstanding random line fetches (latency x
   // concurrency): 8 waves 1.14 ms, 6 waves 1.20, 5 1.27, 4 1.41 at C2 (round-1 occupancy sweep)
   switch (kind) {

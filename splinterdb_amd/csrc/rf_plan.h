@@ -79,7 +79,7 @@ struct FilterPlan {
   uint32_t binsh;         // K4 bins = buckets >> binsh (1: coarse buckets of 2^13 buckets at
                           // load factor ~1, so a workgroup sorts ~8K entries, not ~4K)
   uint32_t cb_base, idx_base, page_base, page_cap, pf_base;
-  // probe lines (device-only, 64 B per group of 2^(lg_line-1) buckets; lg_line 0 = none)
+  // probe lines (device-only, 64 B per group of line_group(lg_line) buckets; lg_line 0 = none)
   uint32_t lg_line, line_base;
   uint32_t lines_asm;  // 1: K6 cuts this filter's lines from its LDS page images; 0: k_plines
   // old filter (incremental add)
@@ -109,6 +109,27 @@ struct FilterPlan {
   // old entries count as none, and K5 takes the old bits over as its own (old_error).
   const FilterOut* old_out;
 };
+// Probe-line geometry named by FilterPlan::lg_line (the top byte of the plan word): 0 = no lines;
+// 1..7 = lines of G = 2^(lg_line - 1) buckets, 128 unary bits and 384 field bits; LINE_DENSE |
+// (G - 1) = the dense format ("probe lines, dense" in rf_kernels.hip): any G <= 64, L = ceil(IS /
+// G) lines per index (the last group of an index is shorter), U unary bits and 512 - U field bits.
+constexpr uint32_t LINE_DENSE = 0x80;
+constexpr uint32_t LINE_UNARY_MAX = 160;  // five dwords of unary code at the most
+__host__ __device__ inline bool line_is_dense(uint32_t lg_line) { return (lg_line & LINE_DENSE) != 0; }
+__host__ __device__ inline uint32_t line_group(uint32_t lg_line) {
+  return line_is_dense(lg_line) ? (lg_line & 0x3fu) + 1u : 1u << (lg_line - 1);
+}
+__host__ __device__ inline uint32_t lines_per_index(uint32_t lis, uint32_t lg_line) {
+  const uint32_t IS = 1u << lis;
+  return line_is_dense(lg_line) ? (IS + line_group(lg_line) - 1) / line_group(lg_line) : IS >> (lg_line - 1);
+}
+// U of a dense line of G buckets: G terminators and cap entries, cap = the entries whose unary
+// bits and rvs-bit fields fill the 512 bits together -- both regions are full at the same count
+__host__ __device__ inline uint32_t line_unary_bits(uint32_t G, uint32_t rvs) {
+  const uint32_t cap = (512u - G) / (1u + rvs), room = LINE_UNARY_MAX - G;
+  return G + (cap < room ? cap : room);
+}
+
 // the error bits of the filter P is built on (device: its build is ordered before P's)
 __host__ __device__ inline uint32_t old_error(const FilterPlan& P) { return P.old_out ? P.old_out->error : 0u; }
 
@@ -267,6 +288,8 @@ struct LaunchArgs {
   uint32_t line_lmax;       // max lines per index over the batch (k_plines LDS sizing)
   uint32_t plines_needed;   // some filter's lines come from k_plines
   uint32_t plines_force;    // k_plines over every filter (diagnostics)
+  uint32_t lines_dense;     // some filter of the batch has dense lines: the kernels that cut and
+                            // probe lines run their DENSE instantiation
   const uint32_t* idx_filter;
   uint32_t num_idx;
   uint32_t* page_first;
