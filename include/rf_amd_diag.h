@@ -85,6 +85,14 @@ uint64_t rf_amd_diag_dense_line_filters(void);
  * sort leaves both unchanged */
 uint64_t rf_amd_diag_part16_builds(void);
 
+/* how many builds of this process were launched packed: bitmap builds whose every filter has a
+ * remainder-and-value field of at most 5 bits and probe lines cut by the assembly kernel, unless
+ * RF_AMD_K4_PACK=0. K4 of such a build writes each index block's body instead of the sorted
+ * entries, and K6 places the bodies in their pages; a build whose partition spills falls back,
+ * on the device, to the sorted entries and is still counted. A batch built this way keeps no
+ * entries: an incremental add onto it decodes its image, as for an imported batch */
+uint64_t rf_amd_diag_k4_packed_builds(void);
+
 /* process-wide cap on the grid of the fan-out probe (rf_amd_filter_set_probe_*), in workgroups
  * of 256 keys; 0 restores the default, a grid that covers n. With a cap below n / 256 every
  * wave takes several 64-key chunks, so a test of a few thousand keys runs the kernel's

@@ -152,6 +152,7 @@ struct BatchPlan {
   bool lay_whole = true;
   std::vector<uint32_t> lay_wg;
   bool k4_bitmap = false;  // K4 runs k_cb_bitmap, not k_cb_sort (k4_bitmap_batch)
+  bool k4_pack = false;    // ... and packs index-block bodies for K6 to place (k4_pack_batch)
   // tile maps of a chained batch: tiles are cut at run boundaries and carry their run's value
   // and end (both relative to the filter's first input, like tile_start)
   std::vector<uint32_t> tile_filter, tile_start, tile_value, tile_end;
@@ -329,6 +330,38 @@ inline bool k4_bitmap_batch(const BatchPlan& b, const rf_amd_config& cfg) {
   return true;
 }
 
+// Packed builds (rf_plan.h: IDX_PACKED): a bitmap batch whose K4 can build every index block's
+// body from its bit set, so that no sorted entries are written and K6 only places the bodies.
+// Bound on the dwords one coarse bucket's bodies take, each starting on a dword. A block of c
+// entries has (c + IS - 1) / 8 + 4 encoding bytes and at most c rvs / 8 + 4 remainder bytes
+// (k_layout's block_size less the 2-byte count), and up to 3 bytes of padding: over the ipc
+// indices of a bucket of `kept` entries that is at most
+//   (kept (1 + rvs) + ipc (IS - 1)) / 8 + 11 ipc   bytes,
+// which grows with kept <= min(SORT_CAP, 2^(bbits + rvs)).
+inline uint32_t k4_pack_bound_dwords(const FilterPlan& p, uint32_t lis) {
+  const uint64_t ipc = 1ull << (p.bbits - lis), IS = 1ull << lis;
+  const uint64_t kept = std::min<uint64_t>(SORT_CAP, 1ull << (p.bbits + p.rvs));
+  return (uint32_t)(((kept * (1 + p.rvs) + ipc * (IS - 1)) / 8 + 11 * ipc) / 4);
+}
+// A filter packs when a bucket of the filter lies inside one word of the bit set (rvs <= 5) and a
+// K4 thread's four words inside one index (lis + rvs >= 7), a coarse bucket's bodies and their
+// starts fit the LDS they are staged in (and with it the bucket's region of `part`), and K6
+// holds every block of a page in its tables: lines_asm says so, and a filter without lines is
+// held to the same bound. (Pages of more blocks are assembled from sorted entries only.)
+inline bool k4_pack_filter(const FilterPlan& p, const rf_amd_config& cfg) {
+  const uint32_t lis = cfg.log_index_size;
+  if (p.rvs > 5 || lis + p.rvs < 7 || p.bbits < lis || (1u << (p.bbits - lis)) > K4_PACK_MAX_IPC) return false;
+  if (k4_pack_bound_dwords(p, lis) > K4_PACK_STAGE_DW) return false;
+  const uint32_t min_block = 2 + ((1u << lis) - 1) / 8 + 4 + 3;  // (lines_in_assembly)
+  return p.lines_asm || (!p.lg_line && cfg.page_size / min_block + 1 <= ASM_MAXB);
+}
+inline bool k4_pack_batch(const BatchPlan& b, const rf_amd_config& cfg) {
+  if (!b.k4_bitmap) return false;
+  for (const FilterPlan& p : b.plans)
+    if (!k4_pack_filter(p, cfg)) return false;
+  return true;
+}
+
 // Old filters of an incremental batch: read in place from their batch's sorted entries when
 // the geometry allows (32-bit pipeline; the old batch built here, not imported), else decoded
 // from the image -- only those join the batch's old-index list and old32
@@ -478,6 +511,7 @@ inline int plan_batch(const BatchInput& in0, const PlanKnobs& knobs, BatchPlan* 
   if (cfg.page_size > MAX_PAGE || F >= (1u << 26)) b.lay_seg = 0;
   assign_layout(b);
   b.k4_bitmap = k4_bitmap_batch(b, cfg);
+  b.k4_pack = k4_pack_batch(b, cfg);
   b.num_tiles = b.pre_of(PRE_TILE)[F];
   b.num_old_tiles = b.pre_of(PRE_OTILE)[F];
   if (b.NL > 0xffffffffull) return plan_fail(err, RF_AMD_EINVAL, "batch too large (probe lines > 2^32)");

@@ -1024,6 +1024,7 @@ static LaunchArgs make_args(rf_amd_batch* b, hipStream_t st) {
   a.lay_seg = b->lay_seg;
   a.lay_whole = b->lay_whole ? 1u : 0u;
   a.k4_bitmap = b->k4_bitmap ? 1u : 0u;
+  a.k4_pack = b->k4_pack ? 1u : 0u;
   a.events = b->events.empty() ? nullptr : reinterpret_cast<void**>(b->events.data() + (size_t)b->ev_set * NUM_EVENTS);
   a.ev_mask = b->ev_mask;
   return a;
@@ -1098,7 +1099,9 @@ static int do_build(rf_amd_batch* b, int kind, const void* in0, const uint64_t* 
   }
   if (int erc = note_built(b, st)) return erc;
   b->built = true;
-  b->has_entries = true;
+  // a packed build leaves index-block bodies in d_part, not sorted entries (unless it spilled,
+  // which the host cannot know): a later add onto this batch decodes its image
+  b->has_entries = !rf_build_packs(&a);
   return 0;
 }
 
@@ -1872,6 +1875,7 @@ extern "C" const char* rf_amd_build_id(void) { return RF_AMD_SRC_ID; }
 extern "C" uint64_t rf_amd_diag_k4_bitmap_builds(void) { return rf_k4_bitmap_builds(); }
 extern "C" uint64_t rf_amd_diag_dense_line_filters(void) { return g_dense_line_filters.load(std::memory_order_relaxed); }
 extern "C" uint64_t rf_amd_diag_part16_builds(void) { return rf_part16_builds(); }
+extern "C" uint64_t rf_amd_diag_k4_packed_builds(void) { return rf_k4_packed_builds(); }
 
 extern "C" int rf_amd_diag_lookup_stats(uint64_t* out, int reset) {
   if (!out) return fail(RF_AMD_EINVAL, "null output");

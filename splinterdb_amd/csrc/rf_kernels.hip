@@ -1127,6 +1127,16 @@ __global__ __launch_bounds__(SORT_NT, 6) void k_cb_sort(const FilterPlan* __rest
   }
 }
 
+// a 64-bit mask ORed into the LDS words at bit `bitpos` (k_cb_bitmap's packed path)
+__device__ __forceinline__ void lds_or_mask64(uint32_t* s, uint32_t bitpos, uint64_t m) {
+  const uint32_t w = bitpos >> 5, sh = bitpos & 31u;
+  const uint64_t lo = m << sh;
+  const uint32_t hi = sh ? (uint32_t)(m >> (64u - sh)) : 0u;
+  if ((uint32_t)lo) atomicOr(&s[w], (uint32_t)lo);
+  if ((uint32_t)(lo >> 32)) atomicOr(&s[w + 1], (uint32_t)(lo >> 32));
+  if (hi) atomicOr(&s[w + 2], hi);
+}
+
 // K4 by bitmap: fresh single-run builds whose entries vary, inside a coarse bucket, only in
 // their low kw = bbits + rvs <= K4_BITMAP_MAX_BITS bits (the bits above are the bucket's number
 // cbl; the host decides, k4_bitmap_batch). Sorting and deduplicating such a bucket is building
@@ -1142,6 +1152,19 @@ __global__ __launch_bounds__(SORT_NT, 6) void k_cb_sort(const FilterPlan* __rest
 // partition's 16-bit keys (k_hash_scatter P16: the host takes both decisions at once), or, after
 // a spill, 32-bit entries at the scanned starts. The sorted entries written over the bucket's
 // own region stay 32-bit; every key of the region is in registers before the first store.
+//
+// PACK (packed builds, k4_pack_batch; rf_plan.h: IDX_PACKED): unless the partition spilled --
+// then the emission above, unchanged -- no sorted entries are written. The bit set holds all
+// that a block's body is made of: bucket b of index l is the 2^rvs bits at b << rvs of the
+// index's words, so its unary code is popc(field) zeros and a one, and its remainder fields are
+// the positions of the set bits inside the field, in order. A thread's four words lie in one
+// index (lis + rvs >= 7); it ORs their codes' ones and their fields into the zeroed staging
+// area (the LDS of s_key, not otherwise used on this path) at the body's start, which one scan
+// over the indices' body sizes gives; the thread of an index's last words adds the ones from
+// the code's end to the end of the encoding bytes. The staged bodies go out with coalesced
+// stores over the bucket's own region (its keys were all read before the first barrier), and
+// idx_start is the body's dword offset | IDX_PACKED.
+template <bool PACK>
 __global__ __launch_bounds__(SORT_NT, 8) void k_cb_bitmap(const FilterPlan* __restrict__ plans,
                                                           const uint32_t* __restrict__ cb_filter,
                                                           const uint32_t* __restrict__ cb_count,
@@ -1194,6 +1217,11 @@ __global__ __launch_bounds__(SORT_NT, 8) void k_cb_bitmap(const FilterPlan* __re
   }
   v4u* bm4 = reinterpret_cast<v4u*>(s_bm) + threadIdx.x;
   *bm4 = v4u{0u, 0u, 0u, 0u};
+  if constexpr (PACK) {
+    static_assert(SORT_CAP * 2 % 16 == 0, "the staging area is cleared in 16-byte stores");
+    if (keys16)
+      for (uint32_t i = threadIdx.x; i < SORT_CAP * 2 / 16; i += SORT_NT) reinterpret_cast<v4u*>(s_key)[i] = v4u{0u, 0u, 0u, 0u};
+  }
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
   __builtin_amdgcn_s_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
@@ -1229,6 +1257,74 @@ __global__ __launch_bounds__(SORT_NT, 8) void k_cb_bitmap(const FilterPlan* __re
   DBG_PHASE(2);
   // word prefixes over this thread's own words (no other thread reads them before the barrier)
   *bm4 = v4u{pos, pos + c0, pos + c0 + c1, pos + c0 + c1 + c2};
+  if constexpr (PACK) {
+    if (keys16) {  // workgroup-uniform: the build did not spill, so every bucket of it packs
+      __syncthreads();
+      DBG_PHASE(5);
+      uint32_t* const stage = reinterpret_cast<uint32_t*>(s_key);
+      uint32_t* const s_boff = stage + K4_PACK_STAGE_DW;  // body start of each index (dwords)
+      const uint32_t rvs = P.rvs, IS = 1u << lis, ipc = 1u << (P.bbits - lis), wsh = lis + rvs - 5u;
+      const uint32_t W0 = threadIdx.x * 4u, l = W0 >> wsh;  // this thread's words, their index
+      const bool live = l < ipc;                           // (a narrower set leaves the upper words unused)
+      const uint32_t lw = min(l, ipc - 1u) << wsh, uw = lw + (1u << wsh);
+      const uint32_t lo = s_bm[lw], c = (uw < BM_WORDS ? s_bm[uw] : kept) - lo;  // the index's first entry, its count
+      const bool first = live && W0 == lw, lastw = live && W0 + 4u == uw;
+      uint32_t tot;
+      const uint32_t boff = block_excl_scan<SORT_NT>(first ? pack_body_dwords(c, IS, rvs) : 0u, s_tmp, &tot);
+      if (first) {
+        s_boff[l] = boff;
+        const uint32_t g = P.idx_base + (cbl << (P.bbits - lis)) + l;
+        idx_cnt[g] = c;
+        idx_start[g] = (cb_rel + boff) | IDX_PACKED;
+      }
+      __syncthreads();
+      if (live) {
+        const uint32_t ebit = s_boff[l] * 32u, rbit = ebit + ((c + IS - 1u) / 8u + 4u) * 8u;
+        const uint32_t ww[4] = {w.x, w.y, w.z, w.w};
+        const uint32_t pw[4] = {pos, pos + c0, pos + c0 + c1, pos + c0 + c1 + c2};
+        const uint32_t nbw = 32u >> rvs, fbits = 1u << rvs;  // buckets per word, bits per bucket
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+          const uint32_t x = ww[j], k0 = pw[j] - lo;        // entries of the index before this word
+          const uint32_t b0 = (W0 + j - lw) << (5u - rvs);  // the word's first bucket in the index
+          // bucket b0 + i ends at code bit b0 + i + (entries in buckets <= b0 + i)
+          uint64_t ones = 0;
+#pragma unroll 1
+          for (uint32_t i = 0; i < nbw; i++) {
+            const uint32_t upto = (i + 1u) * fbits;
+            ones |= 1ull << (i + __popc(upto >= 32u ? x : x & ((1u << upto) - 1u)));
+          }
+          lds_or_mask64(stage, ebit + k0 + b0, ones);
+          if (rvs) {  // fields: the set bits' positions inside their buckets, entry k at k rvs
+            uint32_t y = x, at = rbit + k0 * rvs, nbit = 0;
+            uint64_t acc = 0;
+            while (y) {
+              acc |= (uint64_t)((uint32_t)__builtin_ctz(y) & (fbits - 1u)) << nbit;
+              nbit += rvs;
+              y &= y - 1u;
+              if (nbit > 56u) {  // (rvs <= 5: room for the next field below)
+                lds_or_mask64(stage, at, acc);
+                at += nbit;
+                acc = 0;
+                nbit = 0;
+              }
+            }
+            if (nbit) lds_or_mask64(stage, at, acc);
+          }
+        }
+        // ones from the code's end (c + IS bits) to the end of the encoding bytes: 32..39 bits
+        if (lastw) lds_or_mask64(stage, ebit + c + IS, lowmask64(rbit - ebit - c - IS));
+      }
+      __syncthreads();
+      DBG_PHASE(6);
+      uint32_t* dstp = sorted32 + P.e_first + cb_rel;
+      for (uint32_t i = threadIdx.x; i < min(tot, K4_PACK_STAGE_DW); i += SORT_NT) dstp[i] = stage[i];
+      DBG_PHASE(7);
+      if (threadIdx.x == 0) atomicAdd(&outs[f].num_unique, kept);
+      DBG_PHASE(8);
+      return;
+    }
+  }
   {
     uint32_t p = pos;
     const uint32_t ww[4] = {w.x, w.y, w.z, w.w};
@@ -2591,7 +2687,15 @@ __device__ __forceinline__ uint64_t lds_bits64(const uint32_t* s_pg, uint32_t bi
 // with one atomic: adjacent lanes share at most a window edge. (D) 16-byte stores.
 // Measured before: entry-parallel single-bit atomics (~19 LDS conflict cycles per LDS
 // instruction), and a byte-serial gather per 16-byte chunk (3.6x slower again).
-template <bool DENSE>
+//
+// PACKED (the launch of a packed build, k4_pack_batch): the page's blocks may carry IDX_PACKED
+// on their idx_start -- all of a build's do or none, K4 chose by the build's spill word, which
+// K5 has cleared by now -- and then (B) and (C) are a copy: a block's image is its 16-bit count
+// and the body K4 left at idx_start, so a word of the page is two dwords of that image shifted
+// by the block's byte misalignment, ORed over the (at most three) blocks a 16-byte quad meets;
+// past a block's end its image is zero. The group boundaries of (E) then come from the image,
+// as for pages assembled by atomics (E1).
+template <bool DENSE, bool PACKED = false>
 __global__ __launch_bounds__(ASM_NT) __attribute__((amdgpu_waves_per_eu(8))) void k_assemble(const FilterPlan* __restrict__ plans,
                                                      const uint32_t* __restrict__ pg_filter,
                                                      const uint32_t* __restrict__ idx_cnt,
@@ -2682,7 +2786,62 @@ __global__ __launch_bounds__(ASM_NT) __attribute__((amdgpu_waves_per_eu(8))) voi
   }
   if (threadIdx.x == 0) { s_est[nb] = nruns; s_off[nb] = page_size; }
   DBG_PHASE_K(3, 0);
-  if (ne > ASM_MAXE) {  // uniform (scan total)
+  // (block 0's s_src was written before the scan's barriers)
+  const bool packed = PACKED && (__builtin_amdgcn_readfirstlane(s_src[0]) & IDX_PACKED);
+  if (packed) {
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < 2; q++) {  // word marks of the block starts, as on the current path
+      const uint32_t j = threadIdx.x * 2 + q;
+      if (j < nb && j > 0) reinterpret_cast<uint8_t*>(s_wm)[(oj[q] + 3) / 4] = 1;
+    }
+    __syncthreads();
+    const uint32_t nwp = page_size / 4;
+    constexpr uint32_t QPT = (MAX_PAGE / 16 + ASM_NT - 1) / ASM_NT;
+    uint32_t mwq[QPT], msum = 0;
+#pragma unroll
+    for (uint32_t q = 0; q < QPT; q++) {
+      const uint32_t qd = threadIdx.x * QPT + q;
+      mwq[q] = 4 * qd < nwp ? s_wm[qd] : 0u;
+      msum += (mwq[q] & 0xffu) + ((mwq[q] >> 8) & 0xffu) + ((mwq[q] >> 16) & 0xffu) + (mwq[q] >> 24);
+    }
+    uint32_t mtot;
+    uint32_t jw = block_excl_scan<ASM_NT>(msum, s_tmp, &mtot);
+    const uint32_t* base = sorted32 + P.e_first;
+#pragma unroll
+    for (uint32_t q = 0; q < QPT; q++) {
+      const uint32_t qd = threadIdx.x * QPT + q;
+      const uint32_t mw = mwq[q];
+      if (4 * qd < nwp) {
+        const uint32_t ja = jw + (mw & 0xffu);  // the block holding the quad's first byte
+        jw += (mw & 0xffu) + ((mw >> 8) & 0xffu) + ((mw >> 16) & 0xffu) + (mw >> 24);
+        uint32_t x4[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+        for (uint32_t t = 0; t < 3; t++) {  // blocks are >= 9 bytes: the quad meets ja .. ja + 2
+          const uint32_t j = ja + t;
+          if (j < nb && (t == 0 || s_off[j] < 16 * qd + 16)) {
+            const uint32_t c = s_c[j];
+            const int32_t nd = (int32_t)pack_body_dwords(c, IS, rvs);
+            const uint32_t* src = base + (s_src[j] & ~IDX_PACKED);
+            // image dword k: the count in the upper half of dword -1, the body in 0 .. nd - 1;
+            // s0 = the image byte at the quad's first byte
+            const int32_t s0 = (int32_t)(16 * qd) - (int32_t)s_off[j] - 2, q0 = s0 >> 2;
+            const uint32_t r8 = ((uint32_t)s0 & 3u) * 8u;
+            uint32_t d[5];
+#pragma unroll
+            for (int32_t i = 0; i < 5; i++) {
+              const int32_t k = q0 + i;
+              d[i] = (k >= 0 && k < nd) ? src[k] : (k == -1 ? c << 16 : 0u);
+            }
+#pragma unroll
+            for (int i = 0; i < 4; i++) x4[i] |= r8 ? (d[i] >> r8) | (d[i + 1] << (32u - r8)) : d[i];
+          }
+        }
+        reinterpret_cast<v4u*>(s_pg)[qd] = v4u{x4[0], x4[1], x4[2], x4[3]};
+      }
+    }
+    if (threadIdx.x < 4) s_pg[page_size / 4 + threadIdx.x] = 0;
+  } else if (ne > ASM_MAXE) {  // uniform (scan total)
     __syncthreads();
     assemble_atomic(P, p, slot, b0, b1, idx_cnt, idx_start, sorted32, slots, pages, lis, page_size, s_pg);
   } else {
@@ -2883,7 +3042,7 @@ __global__ __launch_bounds__(ASM_NT) __attribute__((amdgpu_waves_per_eu(8))) voi
     if (threadIdx.x == 0) pg_noline[1 + atomicAdd(&pg_noline[0], 1u)] = slot;  // k_plines_list
     return;
   }
-  if (ne <= ASM_MAXE) {
+  if (!packed && ne <= ASM_MAXE) {
     // the entry runs wrote every group boundary of blocks with entries; the first and end
     // entries of each block and the boundaries of empty blocks here
 #pragma unroll
@@ -5235,10 +5394,30 @@ static std::atomic<uint64_t> g_k4_bitmap_builds{0};
 extern "C" uint64_t rf_k4_bitmap_builds(void) { return g_k4_bitmap_builds.load(std::memory_order_relaxed); }
 static std::atomic<uint64_t> g_part16_builds{0};
 extern "C" uint64_t rf_part16_builds(void) { return g_part16_builds.load(std::memory_order_relaxed); }
+// Packed builds: the bitmap builds the planner marked (LaunchArgs::k4_pack) launch the packed
+// instantiations of K4 and K6; RF_AMD_K4_PACK=0: the sorted entries instead, for A/B.
+// g_k4_packed_builds counts the builds launched packed (rf_amd_diag_k4_packed_builds); whether
+// such a build then spilled, and so wrote sorted entries after all, only the device knows.
+static bool k4_pack_enabled() {
+  static int v = -1;
+  if (v < 0) {
+    const char* e = getenv("RF_AMD_K4_PACK");
+    v = (e && e[0] == '0') ? 0 : 1;
+  }
+  return v != 0;
+}
+static std::atomic<uint64_t> g_k4_packed_builds{0};
+extern "C" uint64_t rf_k4_packed_builds(void) { return g_k4_packed_builds.load(std::memory_order_relaxed); }
+// whether rf_launch_build launches this build packed
+extern "C" int rf_build_packs(const LaunchArgs* pa) {
+  const LaunchArgs& a = *pa;
+  return (!a.tile_value && !a.wide && a.k4_bitmap && a.k4_pack && k4_bitmap_enabled() && k4_pack_enabled()) ? 1 : 0;
+}
 
 // bitmap: K4 as k_cb_bitmap (fresh single-run 32-bit builds only; the partition wrote 16-bit keys)
 template <typename EntT, bool FL = (sizeof(EntT) == 8), bool DUAL = false, bool RUNS = false>
-static int launch_sort_t(const LaunchArgs& a, EntT* ent, EntT* part, const uint32_t* spill, bool bitmap = false) {
+static int launch_sort_t(const LaunchArgs& a, EntT* ent, EntT* part, const uint32_t* spill, bool bitmap = false,
+                         bool pack = false) {
   if constexpr (DUAL) {
     // 32-bit incremental builds: K4m (round-8 K4 2.22 -> 1.48 ms on one box)
     hipLaunchKernelGGL((k_cb_merge<RUNS>), dim3(a.num_cb), dim3(SORT_NT), 0, (hipStream_t)a.stream, a.plans, a.cb_filter,
@@ -5256,10 +5435,11 @@ static int launch_sort_t(const LaunchArgs& a, EntT* ent, EntT* part, const uint3
     if constexpr (sizeof(EntT) == 4 && !FL && !RUNS) {
       if (bitmap) {
         launched = true;
-        hipLaunchKernelGGL(k_cb_bitmap, dim3(a.num_cb), dim3(SORT_NT), 0, (hipStream_t)a.stream, a.plans, a.cb_filter,
+        hipLaunchKernelGGL(pack ? k_cb_bitmap<true> : k_cb_bitmap<false>, dim3(a.num_cb), dim3(SORT_NT), 0, (hipStream_t)a.stream, a.plans, a.cb_filter,
                            a.cb_count, a.cb_start, part, a.sorted32, a.idx_cnt, a.idx_start, a.outs, a.overflow, a.lis,
                            spill);
         g_k4_bitmap_builds.fetch_add(1, std::memory_order_relaxed);
+        if (pack) g_k4_packed_builds.fetch_add(1, std::memory_order_relaxed);
       }
     }
     if (!launched) {
@@ -5295,6 +5475,7 @@ static int launch_plines_list(const LaunchArgs& a) {
 template <bool RUNS>
 static int launch_build_t(const LaunchArgs& a) {
   const TileRuns runs{a.tile_value, a.tile_end};
+  bool pack = false;  // a packed build (fresh bitmap builds only)
   if (a.wide && a.flag32) {
     // incremental add, 32-bit flagged entries (fp_size + value_size <= 31): the new entries
     // are hashed, counted and scattered; each coarse bucket's run of the (sorted) old
@@ -5359,6 +5540,7 @@ static int launch_build_t(const LaunchArgs& a) {
     // only those: one decision for both launches
     bool bitmap = false;
     if constexpr (!RUNS) bitmap = a.k4_bitmap && k4_bitmap_enabled();
+    pack = bitmap && rf_build_packs(&a);  // K4 packs index-block bodies, K6 places them
     if (a.num_tiles) {
 #define L(K) hipLaunchKernelGGL((k_hash_scatter<K, false, RUNS, P16>), dim3(a.num_tiles), dim3(SCAT_NT), 0, (hipStream_t)a.stream, \
                                 a.plans, a.tile_filter, a.tile_start, a.in0, a.offs, a.key_len, a.fp_size, a.seed, \
@@ -5390,7 +5572,7 @@ static int launch_build_t(const LaunchArgs& a) {
     REC(EV_B_SCAN);
     if (int rc = launch_scatter_t<uint32_t, false, RUNS>(a, ent, part, a.spill)) return rc;
     REC(EV_B_SCATTER);
-    if (int rc = launch_sort_t<uint32_t, false, false, RUNS>(a, ent, part, a.spill, bitmap)) return rc;
+    if (int rc = launch_sort_t<uint32_t, false, false, RUNS>(a, ent, part, a.spill, bitmap, pack)) return rc;
   }
   // the build's counters left zero for the next build (a.self_clean: fresh builds)
   const BuildClean clean = a.self_clean ? BuildClean{a.cb_count, a.cb_cursor, a.overflow, a.spill}
@@ -5409,7 +5591,8 @@ static int launch_build_t(const LaunchArgs& a) {
     CHECK_LAUNCH();
   }
   REC(EV_B_LAYOUT);
-  hipLaunchKernelGGL(a.lines_dense ? k_assemble<true> : k_assemble<false>, dim3(a.num_page_slots), dim3(ASM_NT), 0,
+  hipLaunchKernelGGL(pack ? (a.lines_dense ? k_assemble<true, true> : k_assemble<false, true>)
+                          : (a.lines_dense ? k_assemble<true> : k_assemble<false>), dim3(a.num_page_slots), dim3(ASM_NT), 0,
                      (hipStream_t)a.stream, a.plans, a.pg_filter, a.idx_cnt, a.idx_start, a.sorted32, a.slots,
                      a.page_first, a.outs, a.pages, a.lines, a.pg_noline, a.lis, a.page_size);
   CHECK_LAUNCH();

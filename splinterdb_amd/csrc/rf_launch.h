@@ -35,6 +35,11 @@ int rf_launch_place(void* stream, const uint8_t* img, const uint64_t* slots, uin
 uint64_t rf_k4_bitmap_builds(void);
 // builds whose partition wrote 16-bit in-bucket keys for that kernel (k_hash_scatter, P16)
 uint64_t rf_part16_builds(void);
+// whether rf_launch_build launches this build packed (K4 writes index-block bodies instead of
+// sorted entries unless the partition spills: the batch then has no entries for a later add to
+// read in place), and how many builds were
+int rf_build_packs(const rf::LaunchArgs* a);
+uint64_t rf_k4_packed_builds(void);
 // diagnostics build: the buffer the build kernels write their phase clock stamps to
 int rf_debug_set_phase_buffer(uint64_t* d_buf, uint32_t kid);
 

@@ -34,6 +34,22 @@ constexpr uint32_t K4_BITMAP_MAX_BITS = 16;  // 2^16 bits = 8 KiB, one 16-byte a
 // Such a build's partition writes each entry's low 16 bits only (k_hash_scatter, P16), packed
 // from the region's unchanged base, and k_cb_bitmap reads them two to a 32-bit word
 static_assert(SORT_CAP % 2 == 0, "16-bit keys are stored and read in pairs");
+// Packed builds (k_cb_bitmap<true>, k4_pack_batch): K4 writes each index block's body -- the
+// block's bytes after its 2-byte count: unary encoding, then the remainder fields -- instead of
+// the sorted entries, and K6 only places the bodies in their pages. A body starts on a dword,
+// at idx_start (relative to the filter's e_first, like an entry run) with IDX_PACKED set: the
+// mark is what K6 chooses its path by, index by index written by the K4 workgroup that chose.
+constexpr uint32_t IDX_PACKED = 0x80000000u;
+// dwords of the body of a block of c entries: block_size(c) - 2 bytes (k_layout), rounded up
+__host__ __device__ inline uint32_t pack_body_dwords(uint32_t c, uint32_t index_size, uint32_t rvs) {
+  const uint32_t enc = (c + index_size - 1) / 8 + 4, bits = c * rvs;  // (c <= SORT_CAP, rvs <= 5)
+  return (enc + (bits == 0 ? 3u : (bits - 1) / 8 + 4) + 3) / 4;
+}
+// K4 stages a coarse bucket's bodies in the LDS of its 16-bit keys; the top K4_PACK_MAX_IPC
+// dwords of it hold the bodies' starts
+constexpr uint32_t K4_PACK_MAX_IPC = 256;
+constexpr uint32_t K4_PACK_STAGE_DW = SORT_CAP / 2 - K4_PACK_MAX_IPC;
+static_assert(K4_PACK_STAGE_DW <= CB_REGION, "the staged bodies fit the bucket's region of part");
 constexpr int BIG_NT = 1024;
 constexpr int BIG_GRID = 64;
 constexpr int LAYOUT_NT = 1024;
@@ -308,6 +324,7 @@ struct LaunchArgs {
   uint32_t lay_seg;    // indices per layout workgroup (0: one workgroup per filter)
   uint32_t lay_whole;  // some filter of the batch is laid out by one workgroup
   uint32_t k4_bitmap;  // every filter of the batch takes K4's bitmap kernel (BatchPlan::k4_bitmap)
+  uint32_t k4_pack;    // ... and K4 may pack index-block bodies for K6 to place (BatchPlan::k4_pack)
   uint32_t self_clean;  // K5 leaves the build's counters zero: the next build skips k_build_init
   uint32_t zero_outs;   // no k_build_init ran before this build: it zeroes `outs` itself
   const uint64_t* probe_runs;  // probes grouped by filter: runs[f] <= i < runs[f+1] (nullptr: per-probe ids)

@@ -62,7 +62,7 @@ EXPORTED = [
     "rf_amd_found_compact_scratch_bytes", "rf_amd_found_compact",
     "rf_amd_filter_set_probe_var_keys", "rf_amd_batch_probe_var_keys_runs", "rf_amd_filter_lookup_var_keys",
     "rf_amd_diag_fanout_max_blocks", "rf_amd_diag_lookup_paths", "rf_amd_diag_part16_builds",
-    "rf_amd_diag_dense_line_filters",
+    "rf_amd_diag_dense_line_filters", "rf_amd_diag_k4_packed_builds",
     "rf_amd_filter_set_probe_keys_ragged", "rf_amd_filter_set_probe_var_keys_ragged",
     "rf_amd_filter_set_probe_hashes_ragged",
     "rf_amd_filter_set_create_cap", "rf_amd_filter_set_capacity", "rf_amd_filter_set_update",
@@ -182,6 +182,8 @@ def load_library(build_if_missing=True):
     L.rf_amd_diag_dense_line_filters.restype = u64
     L.rf_amd_diag_part16_builds.argtypes = []
     L.rf_amd_diag_part16_builds.restype = u64
+    L.rf_amd_diag_k4_packed_builds.argtypes = []
+    L.rf_amd_diag_k4_packed_builds.restype = u64
     L.rf_amd_batch_num_filters.argtypes = [vp]
     L.rf_amd_batch_num_filters.restype = u32
     L.rf_amd_filter_add.argtypes = [vp, ctypes.POINTER(RfConfig), ctypes.POINTER(RfImage),
