@@ -372,6 +372,59 @@ int rf_amd_range_map_route_var_keys(rf_amd_range_map *m, const uint8_t *d_bytes,
                                     uint64_t n, uint32_t *d_range, uint64_t *d_member_off,
                                     uint32_t *d_member, uint64_t pair_cap, uint64_t *d_total,
                                     void *d_scratch, void *stream);
+/* ---- range maps that follow the trunk: shared segments, stream-ordered updates ----------------
+ * The flat table above stores, for every range, its own copy of the root's bundles and of every
+ * inner node's above it, so a memtable incorporation, a flush or a maplet compaction of an upper
+ * node changes all R lists. A map made from segments stores each contribution once. A segment is
+ * what one (node, pivot) contributes to a lookup path: the member ids of that pivot's live
+ * inflight bundles from inflight_bundle_start (src/trunk.c:1498-1508, :1958-1959), then its
+ * pivot bundle (:6275-6330). The map holds S segments; segment s has a fixed capacity cap[s] and
+ * a current list of len[s] <= cap[s] ids. Range r has a path, a sequence of segment ids from the
+ * root to the leaf, and its list is the concatenation of the current lists of its path's
+ * segments in path order. The route calls, their kernels and their output are those above: the
+ * map keeps a flat table of the same layout and rewrites it on the device after every update.
+ *
+ * create_segments: boundaries as rf_amd_range_map_create. Range r's path is
+ * h_path[h_path_off[r] .. h_path_off[r+1]) (R + 1 non-decreasing offsets), segment s has room for
+ * h_seg_cap[s] ids and starts as h_seg_ids[h_seg_off[s] .. h_seg_off[s+1]) (S + 1 offsets).
+ * Validated on the host, EINVAL before anything is allocated: everything rf_amd_range_map_create
+ * refuses about boundaries, path or segment offsets decreasing, a path entry >= num_segments, an
+ * initial list longer than its capacity, NULL arrays where needed (h_path with every path empty,
+ * h_seg_ids with every list empty and all three segment arrays with num_segments == 0 may be
+ * NULL), and a range whose path's capacities sum to more than 65,535: the capacities, not the
+ * lengths, so that no later update can break the ragged probe's limit. Legal: an empty path (an
+ * empty list), cap == 0, num_segments == 0 with all paths empty, a segment in no path, a segment
+ * twice in one path (its list appears twice). The image -- the flat table flattened on the host,
+ * with room in its list for every path's capacities, the paths, each segment's base, capacity
+ * and length, the segments' id slots and the flatten's tile scratch -- goes into one pool block
+ * by one copy on the engine stream, which is then synchronised, as for the flat create. destroy
+ * and destroy_on are those above. rf_amd_range_map_max_list of such a map is the largest sum of a
+ * path's capacities: a bound for the map's life, so pair_cap = n * max_list never overflows
+ * whatever updates arrive. rf_amd_range_map_num_segments: S (0 also for a flat map and NULL).
+ *
+ * update_segments: segment seg_id[i]'s list becomes h_ids[h_ids_off[i] .. h_ids_off[i+1]) (count
+ * + 1 offsets), asynchronously on stream (NULL = the engine's), with the semantics of
+ * rf_amd_filter_set_update: a route call queued there before it sees the old lists, one queued
+ * after it the new ones. The ids travel in kernel arguments -- the host arrays may be reused on
+ * return -- in as many launches as they need, followed by the three launches that rewrite the
+ * flat table. The call waits for nothing and allocates nothing on the device; the caller orders
+ * other streams against it and serialises calls on one map. An id named twice: the last entry
+ * wins. count == 0 on a map made from segments is OK and touches nothing. EINVAL, every entry
+ * checked before the first launch and nothing changed on the host or the device: a NULL map, a
+ * flat map, NULL arrays with count > 0 (h_ids may be NULL when every list is empty), an id >=
+ * num_segments, a list longer than its segment's capacity, decreasing offsets. If the HIP
+ * runtime refuses a launch the map is good only for destroy.
+ * Boundaries and paths do not change in place: a leaf split or a new level makes a new map. */
+int rf_amd_range_map_create_segments(rf_amd_engine *e, uint32_t num_ranges,
+                                     const uint8_t *h_bound_bytes, const uint64_t *h_bound_off,
+                                     const uint32_t *h_path, const uint64_t *h_path_off,
+                                     uint32_t num_segments, const uint32_t *h_seg_cap,
+                                     const uint32_t *h_seg_ids, const uint64_t *h_seg_off,
+                                     rf_amd_range_map **out);
+uint32_t rf_amd_range_map_num_segments(const rf_amd_range_map *m);
+int rf_amd_range_map_update_segments(rf_amd_range_map *m, const uint32_t *seg_id,
+                                     const uint32_t *h_ids, const uint64_t *h_ids_off,
+                                     uint32_t count, void *stream);
 /* The engine's lookup server: single lookups -- routing_filter_lookup (src/routing_filter.h:
  * 87-92) and routing_filter_lookup_async states (:130-155) -- without a kernel launch per
  * call. A persistent wave (started on demand on a queue of its own, exiting after 400 us

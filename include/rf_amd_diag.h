@@ -108,6 +108,14 @@ int rf_amd_diag_fanout_max_blocks(uint32_t blocks);
  * takes one map on each side of it. Both are constants of the build. */
 uint32_t rf_amd_diag_range_tile(void);
 uint32_t rf_amd_diag_range_lds_ranges(void);
+/* the ids one launch of rf_amd_range_map_update_segments carries when it holds one list: a list
+ * of one id more is cut into two pieces over two launches. The flatten of an update honours
+ * rf_amd_diag_fanout_max_blocks like the route kernels, in tiles of rf_amd_diag_range_tile()
+ * ranges. */
+uint32_t rf_amd_diag_range_seg_launch_ids(void);
+/* the flatten expands a range's list of at most this many ids by one thread and a longer one by
+ * a wave: a test takes lists of exactly this length and of one id more */
+uint32_t rf_amd_diag_range_seg_thread_ids(void);
 
 /* the source id the library was built from (16 hex digits of SHA-256 over the engine's
  * sources and headers, splinterdb_amd/build.py source_id): the Python loader refuses a

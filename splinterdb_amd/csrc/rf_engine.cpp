@@ -2290,12 +2290,38 @@ extern "C" int rf_amd_found_compact(rf_amd_engine* e, const uint64_t* d_found, u
 // The map is the planner's image (rf_range_plan.h) in one pool block, immutable; a route call is
 // three launches over it and the caller's buffers (rf_range.hip). It holds no reference to any
 // set or batch, and nothing downstream reads it: the route output is a copy.
+// A map made from segments (rf_range_seg_plan.h) also keeps the segment sections' addresses, the
+// capacities for the validation of an update, and the host scratch of an update call.
 struct rf_amd_range_map {
   rf_amd_engine* eng = nullptr;
   uint32_t num_ranges = 0, max_list = 0;
   DevBuf d_image;
   RangeDev dev{};
+  bool segmented = false;
+  RangeSegDev seg{};
+  RangeSegState seg_state;
+  RangeSegUpdatePlan upd_plan;
+  RangeSegUpdate upd_args{};
 };
+
+// the image in one pool block by one copy on the engine stream, which is synchronised: the image
+// is pageable, and route calls may run on any stream
+static int range_map_upload(rf_amd_range_map* m, rf_amd_engine* e, const RangePlan& plan) {
+  m->eng = e;
+  m->num_ranges = plan.num_ranges;
+  m->max_list = plan.max_list;
+  if (m->d_image.alloc(plan.image.size(), &e->pool)) return RF_AMD_ENOMEM;
+  HIPCHK(hipMemcpyAsync(m->d_image.p, plan.image.data(), plan.image.size(), hipMemcpyHostToDevice, e->stream));
+  HIPCHK(hipStreamSynchronize(e->stream));
+  const uint8_t* base = m->d_image.as<uint8_t>();
+  m->dev.num_ranges = plan.num_ranges;
+  m->dev.prefix = reinterpret_cast<const uint64_t*>(base + plan.o_prefix);
+  m->dev.boff = reinterpret_cast<const uint64_t*>(base + plan.o_boff);
+  m->dev.loff = reinterpret_cast<const uint64_t*>(base + plan.o_loff);
+  m->dev.list = reinterpret_cast<const uint32_t*>(base + plan.o_list);
+  m->dev.bytes = base + plan.o_bytes;
+  return 0;
+}
 
 extern "C" int rf_amd_range_map_create(rf_amd_engine* e, uint32_t num_ranges, const uint8_t* h_bound_bytes,
                                        const uint64_t* h_bound_off, const uint32_t* h_list,
@@ -2309,21 +2335,61 @@ extern "C" int rf_amd_range_map_create(rf_amd_engine* e, uint32_t num_ranges, co
     return fail(rc, msg);
   HIPCHK(hipSetDevice(e->device));
   auto m = std::make_unique<rf_amd_range_map>();
-  m->eng = e;
-  m->num_ranges = plan.num_ranges;
-  m->max_list = plan.max_list;
-  if (m->d_image.alloc(plan.image.size(), &e->pool)) return RF_AMD_ENOMEM;
-  HIPCHK(hipMemcpyAsync(m->d_image.p, plan.image.data(), plan.image.size(), hipMemcpyHostToDevice, e->stream));
-  HIPCHK(hipStreamSynchronize(e->stream));  // the image is pageable; route calls may run on any stream
-  const uint8_t* base = m->d_image.as<uint8_t>();
-  m->dev.num_ranges = plan.num_ranges;
-  m->dev.prefix = reinterpret_cast<const uint64_t*>(base + plan.o_prefix);
-  m->dev.boff = reinterpret_cast<const uint64_t*>(base + plan.o_boff);
-  m->dev.loff = reinterpret_cast<const uint64_t*>(base + plan.o_loff);
-  m->dev.list = reinterpret_cast<const uint32_t*>(base + plan.o_list);
-  m->dev.bytes = base + plan.o_bytes;
+  if (int rc = range_map_upload(m.get(), e, plan)) return rc;
   *out = m.release();
   return 0;
+}
+
+extern "C" int rf_amd_range_map_create_segments(rf_amd_engine* e, uint32_t num_ranges, const uint8_t* h_bound_bytes,
+                                                const uint64_t* h_bound_off, const uint32_t* h_path,
+                                                const uint64_t* h_path_off, uint32_t num_segments,
+                                                const uint32_t* h_seg_cap, const uint32_t* h_seg_ids,
+                                                const uint64_t* h_seg_off, rf_amd_range_map** out) {
+  if (!e) return fail(RF_AMD_ENODEV, "no engine");
+  if (!out) return fail(RF_AMD_EINVAL, "null out-param");
+  *out = nullptr;
+  RangeSegPlan plan;
+  std::string msg;
+  if (int rc = plan_range_map_segments(num_ranges, h_bound_bytes, h_bound_off, h_path, h_path_off, num_segments,
+                                       h_seg_cap, h_seg_ids, h_seg_off, &plan, &msg))
+    return fail(rc, msg);
+  HIPCHK(hipSetDevice(e->device));
+  auto m = std::make_unique<rf_amd_range_map>();
+  m->segmented = true;
+  m->seg_state.init(h_seg_cap, num_segments);
+  if (int rc = range_map_upload(m.get(), e, plan)) return rc;
+  m->seg = range_seg_dev(plan, m->d_image.as<uint8_t>());
+  m->upd_args.slots = m->seg.slots;
+  m->upd_args.slen = m->seg.slen;
+  m->upd_args.sbase = m->seg.sbase;
+  m->upd_args.scap = m->seg.scap;
+  m->upd_args.num_segments = num_segments;
+  *out = m.release();
+  return 0;
+}
+
+// Segment lists replaced in stream order: every entry is validated and the call cut into launches
+// on the host (rf_range_seg_plan.h) before the first launch; the scatter launches carry the ids
+// in their arguments, then the flatten rewrites the flat table the route kernels read. Nothing
+// is waited for and nothing allocated on the device. The call's host scratch lives in the map,
+// so the caller serialises calls on one map. A launch the runtime refuses leaves the segments
+// and the flat table out of step: the map is then good only for destroy (rf_amd.h).
+extern "C" int rf_amd_range_map_update_segments(rf_amd_range_map* m, const uint32_t* seg_id, const uint32_t* h_ids,
+                                                const uint64_t* h_ids_off, uint32_t count, void* stream) {
+  if (!m) return fail(RF_AMD_EINVAL, "null range map");
+  if (!m->segmented) return fail(RF_AMD_EINVAL, "a flat range map has no segments");
+  if (count == 0) return 0;
+  std::string msg;
+  if (int rc = plan_range_seg_update(&m->seg_state, count, seg_id, h_ids, h_ids_off, &m->upd_plan, &msg))
+    return fail(rc, msg);
+  HIPCHK(hipSetDevice(m->eng->device));
+  (void)hipGetLastError();
+  hipStream_t st = stream_of(m->eng, stream);
+  for (uint32_t l = 0; l < m->upd_plan.launches(); l++) {
+    range_seg_fill_launch(m->upd_plan, l, h_ids, &m->upd_args);
+    if (int rc = launch_rc("segment update", rf_launch_range_seg_scatter(st, &m->upd_args))) return rc;
+  }
+  return launch_rc("segment flatten", rf_launch_range_seg_flatten(st, &m->seg));
 }
 
 // synchronises the device (route calls on a caller's stream may still read the image), as
@@ -2348,6 +2414,11 @@ extern "C" int rf_amd_range_map_destroy_on(rf_amd_range_map* m, void* stream) {
 
 extern "C" uint32_t rf_amd_range_map_num_ranges(const rf_amd_range_map* m) { return m ? m->num_ranges : 0; }
 extern "C" uint32_t rf_amd_range_map_max_list(const rf_amd_range_map* m) { return m ? m->max_list : 0; }
+extern "C" uint32_t rf_amd_range_map_num_segments(const rf_amd_range_map* m) {
+  return m && m->segmented ? m->seg.num_segments : 0;
+}
+extern "C" uint32_t rf_amd_diag_range_seg_launch_ids(void) { return RANGE_SEG_LAUNCH_IDS; }
+extern "C" uint32_t rf_amd_diag_range_seg_thread_ids(void) { return RANGE_SEG_THREAD_IDS; }
 extern "C" uint64_t rf_amd_range_route_scratch_bytes(uint64_t n) { return range_route_scratch_bytes(n); }
 extern "C" uint32_t rf_amd_diag_range_lds_ranges(void) { return RANGE_LDS_RANGES; }
 extern "C" uint32_t rf_amd_diag_range_tile(void) { return RANGE_TILE; }

@@ -6,6 +6,7 @@
 
 #include "rf_plan.h"
 #include "rf_range_plan.h"
+#include "rf_range_seg_plan.h"
 
 extern "C" {
 
@@ -82,7 +83,14 @@ int rf_launch_found_compact(void* stream, const uint64_t* found, uint64_t m, uin
 int rf_launch_range_route(void* stream, int var, const uint8_t* keys, const uint64_t* offs, uint32_t key_len,
                           uint64_t n, const rf::RangeDev* m, uint32_t* range, uint64_t* member_off,
                           uint32_t* member, uint64_t pair_cap, uint64_t* total, void* scratch);
-// diagnostics (rf_amd_diag_fanout_max_blocks): a cap on the route kernels' grids; 0 = none
+// k_range_seg_scatter: one launch of a segment update, a->npieces pieces and their ids in the
+// arguments (rf_range_seg_plan.h)
+int rf_launch_range_seg_scatter(void* stream, const rf::RangeSegUpdate* a);
+// k_range_seg_len, k_range_scan, k_range_seg_emit: loff[0..R] and list rewritten from the
+// segments' current lists
+int rf_launch_range_seg_flatten(void* stream, const rf::RangeSegDev* d);
+// diagnostics (rf_amd_diag_fanout_max_blocks): a cap on the route and flatten kernels' grids; 0 =
+// none
 void rf_range_set_max_blocks(uint32_t blocks);
 
 // ---- estimate, hashing, routing, verify ---------------------------------------------------

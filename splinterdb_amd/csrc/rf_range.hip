@@ -241,6 +241,120 @@ __global__ __launch_bounds__(RG_NT) void k_range_emit(const uint32_t* __restrict
   }
 }
 
+// ---- maps made from segments (rf_range_seg_plan.h) -------------------------------------------
+// rf_amd_range_map_update_segments: the scatter stores the new ids and lengths of the named
+// segments, then the flatten rewrites loff[0..R] and list from the segments in three launches
+// without communication between workgroups, the shape of a route call:
+//   k_range_seg_len    one range per lane: its length = the sum of its path's segment lengths;
+//                      the sum of a tile of RANGE_TILE ranges to tcnt[tile]
+//   k_range_scan       as above, over the tile sums; the total to loff[R]
+//   k_range_seg_emit   scans its tile's lengths in the workgroup, writes loff[r], then walks each
+//                      range's path and copies the segments' ids: a thread per short range, a
+//                      wave per long one, 64 ids at a time
+// All in stream order: a route call queued before the update reads the old table, one queued
+// after it the new. The flat table keeps its addresses and layout.
+
+// One launch of an update: wave w takes pieces w, w + RG_NW, ...; the lanes copy the piece's ids
+// from the kernel's arguments into the segment's slots, and lane 0 stores the new length where
+// the piece is a list's last. The host sends no segment twice in one launch, none >=
+// num_segments and no list longer than its capacity; the guards keep a broken argument block
+// from writing outside the segment all the same.
+__global__ __launch_bounds__(RG_NT) void k_range_seg_scatter(RangeSegUpdate a) {
+  const uint32_t lane = threadIdx.x & (WAVE - 1);
+  const uint32_t np = a.npieces < RANGE_SEG_WORDS / RANGE_SEG_PIECE_WORDS ? a.npieces
+                                                                          : RANGE_SEG_WORDS / RANGE_SEG_PIECE_WORDS;
+  for (uint32_t k = threadIdx.x / WAVE; k < np; k += RG_NW) {
+    const uint32_t* w = a.w + RANGE_SEG_PIECE_WORDS * k;
+    const uint32_t seg = w[0], dst = w[1], src = w[2], n = w[3], len = w[4];
+    if (seg >= a.num_segments) continue;
+    const uint32_t cap = a.scap[seg];
+    uint32_t* out = a.slots + a.sbase[seg];
+    for (uint32_t i = lane; i < n; i += WAVE)
+      if ((uint64_t)dst + i < cap && src + i < RANGE_SEG_WORDS) out[dst + i] = a.w[src + i];
+    if (lane == 0 && len != RANGE_SEG_NO_LEN) a.slen[seg] = len < cap ? len : cap;
+  }
+}
+
+// the current length of range r's list
+__device__ __forceinline__ uint32_t seg_range_len(const RangeSegDev& d, uint64_t r) {
+  uint32_t n = 0;
+  for (uint64_t p = d.poff[r], e = d.poff[r + 1]; p < e; p++) n += d.slen[d.path[p]];
+  return n;
+}
+
+__global__ __launch_bounds__(RG_NT) void k_range_seg_len(RangeSegDev d, uint64_t ntiles) {
+  __shared__ uint32_t s_c[RG_NW];
+  for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const uint64_t t0 = t * RANGE_TILE;
+    uint32_t c = 0;
+#pragma unroll
+    for (int q = 0; q < RG_PER; q++) {
+      const uint64_t r = t0 + (uint64_t)q * RG_NT + threadIdx.x;
+      if (r < d.num_ranges) c += seg_range_len(d, r);
+    }
+    const uint32_t s = block_sum<RG_NT>(c, s_c);
+    if (threadIdx.x == 0) d.tcnt[t] = s;
+  }
+}
+
+// A range of at most RANGE_SEG_THREAD_IDS ids is copied by its own thread, so that a tile of
+// short lists -- the trunk's shape -- is expanded by all its threads at once; a longer one by a
+// wave, 64 ids at a time. s_roff: each range's first id relative to the tile's, and the tile's
+// count behind them.
+__global__ __launch_bounds__(RG_NT) void k_range_seg_emit(RangeSegDev d, uint64_t ntiles) {
+  __shared__ uint32_t s_w[RG_PER * RG_NW + 1];
+  __shared__ uint32_t s_roff[RANGE_TILE + 1];
+  const uint32_t lane = threadIdx.x & (WAVE - 1);
+  const uint32_t wv = threadIdx.x / WAVE;
+  const uint64_t R = d.num_ranges;
+  for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const uint64_t t0 = t * RANGE_TILE;
+    uint32_t x[RG_PER], len[RG_PER];
+#pragma unroll
+    for (int q = 0; q < RG_PER; q++) {
+      const uint64_t r = t0 + (uint64_t)q * RG_NT + threadIdx.x;
+      x[q] = len[q] = r < R ? seg_range_len(d, r) : 0u;
+    }
+    uint32_t tot;
+    block_excl_scan_kmajor<RG_NT, RG_PER>(x, s_w, &tot);  // range order: k-major, thread-minor
+    const uint64_t base = d.toff[t];
+#pragma unroll
+    for (int q = 0; q < RG_PER; q++) {
+      const uint32_t j = (uint32_t)q * RG_NT + threadIdx.x;
+      s_roff[j] = x[q];
+      if (t0 + j < R) d.loff[t0 + j] = base + x[q];
+    }
+    if (threadIdx.x == 0) s_roff[RANGE_TILE] = tot;
+#pragma unroll
+    for (int q = 0; q < RG_PER; q++) {
+      if (len[q] == 0 || len[q] > RANGE_SEG_THREAD_IDS) continue;  // len > 0: the range is below R
+      const uint64_t r = t0 + (uint64_t)q * RG_NT + threadIdx.x;
+      uint64_t at = base + x[q];
+      for (uint64_t p = d.poff[r], e = d.poff[r + 1]; p < e; p++) {
+        const uint32_t s = d.path[p], n = d.slen[s];
+        const uint32_t* src = d.slots + d.sbase[s];
+        for (uint32_t i = 0; i < n; i++)
+          if (at + i < d.list_cap) d.list[at + i] = src[i];
+        at += n;
+      }
+    }
+    __syncthreads();
+    const uint32_t nr = R - t0 < RANGE_TILE ? (uint32_t)(R - t0) : RANGE_TILE;
+    for (uint32_t j = wv; j < nr; j += RG_NW) {
+      if (s_roff[j + 1] - s_roff[j] <= RANGE_SEG_THREAD_IDS) continue;  // uniform over the wave
+      uint64_t at = base + s_roff[j];
+      for (uint64_t p = d.poff[t0 + j], e = d.poff[t0 + j + 1]; p < e; p++) {
+        const uint32_t s = d.path[p], n = d.slen[s];
+        const uint32_t* src = d.slots + d.sbase[s];
+        for (uint32_t i = lane; i < n; i += WAVE)
+          if (at + i < d.list_cap) d.list[at + i] = src[i];
+        at += n;
+      }
+    }
+    __syncthreads();  // the next tile's offsets overwrite this one's
+  }
+}
+
 // diagnostics (rf_amd_diag_fanout_max_blocks): a cap on the grids below, so that a route call
 // over a few tiles runs every grid-stride loop more than once per workgroup; 0 = none
 std::atomic<uint32_t> g_range_max_blocks{0};
@@ -249,6 +363,27 @@ std::atomic<uint32_t> g_range_max_blocks{0};
 
 extern "C" void rf_range_set_max_blocks(uint32_t blocks) {
   g_range_max_blocks.store(blocks, std::memory_order_relaxed);
+}
+
+extern "C" int rf_launch_range_seg_scatter(void* stream, const rf::RangeSegUpdate* a) {
+  if (a->npieces == 0) return 0;
+  if (a->npieces > RANGE_SEG_WORDS / RANGE_SEG_PIECE_WORDS) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_range_seg_scatter, dim3(1), dim3(RG_NT), 0, (hipStream_t)stream, *a);
+  return launch_status();
+}
+
+extern "C" int rf_launch_range_seg_flatten(void* stream, const rf::RangeSegDev* d) {
+  const uint64_t ntiles = range_route_tiles(d->num_ranges);
+  hipStream_t st = (hipStream_t)stream;
+  uint64_t nblk = ntiles < RG_MAX_GRID ? ntiles : RG_MAX_GRID;
+  const uint32_t cap = g_range_max_blocks.load(std::memory_order_relaxed);
+  if (cap && nblk > cap) nblk = cap;
+  const dim3 g((uint32_t)nblk), b(RG_NT);
+  hipLaunchKernelGGL(k_range_seg_len, g, b, 0, st, *d, ntiles);
+  hipLaunchKernelGGL(k_range_scan, dim3(1), dim3(1024), 0, st, d->tcnt, ntiles, d->toff, d->toff + ntiles,
+                     d->loff + d->num_ranges);
+  hipLaunchKernelGGL(k_range_seg_emit, g, b, 0, st, *d, ntiles);
+  return launch_status();
 }
 
 extern "C" int rf_launch_range_route(void* stream, int var, const uint8_t* keys, const uint64_t* offs,

@@ -71,6 +71,21 @@ inline uint64_t range_route_tiles(uint64_t n) { return (n + RANGE_TILE - 1) / RA
 // 8 bytes of offset and 4 of pair count per tile, and slack to keep both aligned
 inline uint64_t range_route_scratch_bytes(uint64_t n) { return ((12 * range_route_tiles(n) + 15) & ~15ull) + 16; }
 
+// what both creates refuse about the R - 1 boundaries of R >= 1 ranges: the message, or nullptr
+inline const char* range_bounds_refusal(uint32_t R, const uint8_t* bound_bytes, const uint64_t* bound_off) {
+  if (R > 1 && !bound_off) return "null boundary offsets";
+  for (uint32_t j = 0; j + 1 < R; j++)
+    if (bound_off[j + 1] < bound_off[j]) return "boundary offsets decrease";
+  const uint64_t nbytes = R > 1 ? bound_off[R - 1] - bound_off[0] : 0;
+  if (nbytes && !bound_bytes) return "null boundary bytes";
+  for (uint32_t j = 0; j + 2 < R; j++) {
+    const uint64_t a = bound_off[j], b = bound_off[j + 1], c = bound_off[j + 2];
+    // strictly ascending: NOT (boundary[j + 1] <= boundary[j])
+    if (range_key_le(bound_bytes + b, c - b, bound_bytes + a, b - a)) return "boundaries not strictly ascending";
+  }
+  return nullptr;
+}
+
 inline int plan_range_map(uint32_t num_ranges, const uint8_t* bound_bytes, const uint64_t* bound_off,
                           const uint32_t* list, const uint64_t* list_off, RangePlan* plan, std::string* err) {
   auto refuse = [&](const char* m) {
@@ -81,17 +96,8 @@ inline int plan_range_map(uint32_t num_ranges, const uint8_t* bound_bytes, const
   const uint32_t R = num_ranges;
   if (R == 0) return refuse("num_ranges == 0");
   if (!list_off) return refuse("null list offsets");
-  if (R > 1 && !bound_off) return refuse("null boundary offsets");
-  for (uint32_t j = 0; j + 1 < R; j++)
-    if (bound_off[j + 1] < bound_off[j]) return refuse("boundary offsets decrease");
+  if (const char* m = range_bounds_refusal(R, bound_bytes, bound_off)) return refuse(m);
   const uint64_t nbytes = R > 1 ? bound_off[R - 1] - bound_off[0] : 0;
-  if (nbytes && !bound_bytes) return refuse("null boundary bytes");
-  for (uint32_t j = 0; j + 2 < R; j++) {
-    const uint64_t a = bound_off[j], b = bound_off[j + 1], c = bound_off[j + 2];
-    // strictly ascending: NOT (boundary[j + 1] <= boundary[j])
-    if (range_key_le(bound_bytes + b, c - b, bound_bytes + a, b - a))
-      return refuse("boundaries not strictly ascending");
-  }
   uint32_t max_list = 0;
   for (uint32_t r = 0; r < R; r++) {
     if (list_off[r + 1] < list_off[r]) return refuse("list offsets decrease");

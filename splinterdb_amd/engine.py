@@ -71,6 +71,8 @@ EXPORTED = [
     "rf_amd_range_map_num_ranges", "rf_amd_range_map_max_list", "rf_amd_range_route_scratch_bytes",
     "rf_amd_range_map_route_keys", "rf_amd_range_map_route_var_keys",
     "rf_amd_diag_range_tile", "rf_amd_diag_range_lds_ranges",
+    "rf_amd_range_map_create_segments", "rf_amd_range_map_num_segments", "rf_amd_range_map_update_segments",
+    "rf_amd_diag_range_seg_launch_ids", "rf_amd_diag_range_seg_thread_ids",
 ]
 ROUTE_MAX_WORLD = 16
 FOUND_COMPACT_TILE = 4096  # found words per workgroup of rf_amd_found_compact (FC_TILE)
@@ -284,6 +286,14 @@ def load_library(build_if_missing=True):
     L.rf_amd_diag_range_tile.restype = u32
     L.rf_amd_diag_range_lds_ranges.argtypes = []
     L.rf_amd_diag_range_lds_ranges.restype = u32
+    L.rf_amd_range_map_create_segments.argtypes = [vp, u32, vp, vp, vp, vp, u32, vp, vp, vp, ctypes.POINTER(vp)]
+    L.rf_amd_range_map_num_segments.argtypes = [vp]
+    L.rf_amd_range_map_num_segments.restype = u32
+    L.rf_amd_range_map_update_segments.argtypes = [vp, vp, vp, vp, u32, vp]
+    L.rf_amd_diag_range_seg_launch_ids.argtypes = []
+    L.rf_amd_diag_range_seg_launch_ids.restype = u32
+    L.rf_amd_diag_range_seg_thread_ids.argtypes = []
+    L.rf_amd_diag_range_seg_thread_ids.restype = u32
     L.rf_amd_host_alloc.argtypes = [vp, u64, ctypes.POINTER(vp)]
     L.rf_amd_host_free.argtypes = [vp, vp]
     L.rf_amd_host_free.restype = None
@@ -1247,14 +1257,42 @@ def range_route_scratch_bytes(n) -> int:
     return int(load_library().rf_amd_range_route_scratch_bytes(n))
 
 
+def diag_range_seg_launch_ids() -> int:
+    """the ids one launch of RangeMap.update_segments carries when it holds one list
+    (rf_amd_diag_range_seg_launch_ids): a list of one id more is cut into two pieces"""
+    return int(load_library().rf_amd_diag_range_seg_launch_ids())
+
+
+def diag_range_seg_thread_ids() -> int:
+    """the longest list of a range that the flatten of an update expands by a single thread
+    (rf_amd_diag_range_seg_thread_ids); a longer one takes a wave"""
+    return int(load_library().rf_amd_diag_range_seg_thread_ids())
+
+
+def range_segment_lists(paths, seg_lists):
+    """The R flat lists of a map made from segments, as range_route_host and RangeMap take them:
+    range r's list is the concatenation of seg_lists[s] for s in paths[r], in path order."""
+    seg_lists = [[int(i) for i in x] for x in seg_lists]
+    return [[i for s in path for i in seg_lists[s]] for path in paths]
+
+
+def _csr(seqs, dtype):
+    """(flat array of `dtype` with one spare element, uint64 offsets) of a list of sequences"""
+    off = np.zeros(len(seqs) + 1, dtype=np.uint64)
+    np.cumsum(np.array([len(x) for x in seqs], dtype=np.uint64), out=off[1:])
+    flat = np.fromiter((i for x in seqs for i in x), dtype=dtype, count=int(off[-1]))
+    return np.ascontiguousarray(np.append(flat, dtype(0))), off
+
+
 _route_scratch = {}  # (engine, stream) -> the scratch of the last route call issued there
 
 
 class RangeMap:
-    """A resident, immutable table of R key ranges and their member lists (rf_amd_range_map):
+    """A resident table of R key ranges and their member lists (rf_amd_range_map):
     boundaries = the R - 1 boundary keys as `bytes`, strictly ascending in `bytes` order; lists =
     R sequences of member ids (of whatever FilterSet the caller probes), each of at most 65,535.
-    Range r holds the keys k with boundaries[r-1] <= k < boundaries[r]."""
+    Range r holds the keys k with boundaries[r-1] <= k < boundaries[r]. A map made this way is
+    immutable; one made by from_segments follows the trunk through update_segments."""
 
     def __init__(self, boundaries, lists, engine=None):
         self.engine = engine or default_engine()
@@ -1274,7 +1312,59 @@ class RangeMap:
                                                       flat.ctypes.data, loff.ctypes.data, ctypes.byref(h)))
         self.h = h
         self.num_ranges = R
+        self.num_segments = 0
         self.max_list = int(load_library().rf_amd_range_map_max_list(h))
+
+    @staticmethod
+    def _bound_arrays(boundaries, R):
+        boundaries = [bytes(b) for b in boundaries]
+        if R != len(boundaries) + 1:
+            raise ValueError("R ranges take R - 1 boundaries")
+        boff = np.zeros(max(R, 1), dtype=np.uint64)
+        np.cumsum(np.array([len(b) for b in boundaries], dtype=np.uint64), out=boff[1:R])
+        return np.frombuffer(b"".join(boundaries) + b"\0", dtype=np.uint8), boff
+
+    @classmethod
+    def from_segments(cls, boundaries, paths, seg_lists, seg_caps=None, engine=None):
+        """rf_amd_range_map_create_segments: R = len(paths) ranges; paths[r] = range r's segment
+        ids, root to leaf; seg_lists[s] = segment s's initial ids; seg_caps[s] = the ids it has
+        room for (None: its initial length). Range r's list is the concatenation of its path's
+        segments' current lists (range_segment_lists); max_list is the largest sum of a path's
+        capacities, which no update can exceed."""
+        self = cls.__new__(cls)
+        self.h = None
+        self.engine = engine or default_engine()
+        R, S = len(paths), len(seg_lists)
+        bbytes, boff = cls._bound_arrays(boundaries, R)
+        path, poff = _csr(paths, np.uint32)
+        ids, soff = _csr(seg_lists, np.uint32)
+        caps = [len(x) for x in seg_lists] if seg_caps is None else seg_caps
+        if len(caps) != S:
+            raise ValueError("seg_caps and seg_lists differ in length")
+        caps = np.ascontiguousarray(np.append(np.asarray(caps, dtype=np.uint32), np.uint32(0)))
+        h = ctypes.c_void_p()
+        _check(load_library().rf_amd_range_map_create_segments(
+            self.engine.h, R, bbytes.ctypes.data, boff.ctypes.data, path.ctypes.data, poff.ctypes.data, S,
+            caps.ctypes.data, ids.ctypes.data, soff.ctypes.data, ctypes.byref(h)))
+        self.h = h
+        self.num_ranges = R
+        self.num_segments = int(load_library().rf_amd_range_map_num_segments(h))
+        self.max_list = int(load_library().rf_amd_range_map_max_list(h))
+        return self
+
+    def update_segments(self, ids, lists, stream=None):
+        """rf_amd_range_map_update_segments: segment ids[i]'s list becomes lists[i], in stream
+        order and without a host wait -- a route call queued on `stream` before the call sees the
+        old lists, one queued after it the new ones. An id named twice: the last entry wins. The
+        caller orders other streams and serialises calls on one map."""
+        ids = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+        lists = list(lists)
+        if len(lists) != ids.size:
+            raise ValueError("ids and lists differ in length")
+        flat, off = _csr(lists, np.uint32)
+        _check(load_library().rf_amd_range_map_update_segments(
+            self.h, ids.ctypes.data if ids.size else None, flat.ctypes.data if ids.size else None,
+            off.ctypes.data if ids.size else None, ids.size, _stream(stream)))
 
     def close(self):
         if getattr(self, "h", None):

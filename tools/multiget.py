@@ -50,10 +50,23 @@ argument arrays are built beforehand), and the HIP-event time from before the ca
 probe (the stream is idle at the first event, so this interval contains the host time). Default output: profiles/multiget_update.json (measured with
 --filters 1024 --keys 4096).
 
+--segments: what the most frequent trunk event does to a resident range map, two ways. The table is
+trunk-shaped: R = 4,096 leaves, fan-out 16 per level, so a leaf's path has 4 segments (the root's
+pivot, two inner pivots, the leaf's own), each with 1 to 8 ids and room for 8. One root segment
+changes. (a) rf_amd_range_map_update_segments of that segment on a map made from segments
+(E.RangeMap.from_segments): one scatter launch and the three of the flatten. (b) what a flat map
+needs: rf_amd_range_map_create of the rebuilt flat table and rf_amd_range_map_destroy_on of the old
+map. Reported per way, minimum to maximum over the alternating rounds: the host wall time of the C
+calls (arrays built beforehand) and the HIP-event time around them on the idle stream; (b) also
+through E.RangeMap(...) + close_on. A route call of 2^20 24-byte keys is timed on the segmented map
+before and after every update and on the flat map. Both ways' route output after the same change
+is compared over all keys before anything is timed. Default output: profiles/range_segments.json.
+
     timeout -k 10 600 python tools/multiget.py [--var] [--ragged | --routed] [--filters 64] [--keys 1048576]
                                                [--n 16777216] [--k 4] [--rounds 7] [--warmup 2]
                                                [--out profiles/multiget.json]
     timeout -k 10 300 python tools/multiget.py --update --filters 1024 --keys 4096
+    timeout -k 10 300 python tools/multiget.py --segments
 """
 import argparse
 import json
@@ -502,6 +515,185 @@ def update_mode(args):
     eng.close()
 
 
+SEG_R, SEG_FAN, SEG_N = 4096, 16, 1 << 20  # --segments: leaves, fan-out per level, keys of a route call
+
+
+def segments_mode(args):
+    """--segments: a trunk change to a resident range map, two ways; see the module docstring"""
+    import ctypes
+    import time
+
+    import numpy as np
+    R, fan, n = SEG_R, SEG_FAN, SEG_N
+    dev = torch.device("cuda:0")
+    eng = E.Engine(0)
+    L = E.load_library()
+    stream = torch.cuda.Stream(device=dev)
+    st = stream.cuda_stream
+    hr = np.random.default_rng(17)
+    # three levels of inner nodes above the leaves: leaf r's path is the root's pivot, the pivot of
+    # each inner node below it, and the leaf's own segment
+    widths = [fan, fan * fan, R, R]
+    first = np.concatenate([[0], np.cumsum(widths)]).tolist()
+    S = first[-1]
+    paths = [[first[0] + r // (R // widths[0]), first[1] + r // (R // widths[1]), first[2] + r, first[3] + r]
+             for r in range(R)]
+    cap = 8
+    seg_lists = [hr.integers(0, 1024, size=int(hr.integers(1, cap + 1))).tolist() for _ in range(S)]
+    pool = sorted({bytes(b) for b in hr.integers(0, 256, size=(R + 64, 24), dtype=np.uint8)})
+    bounds = [pool[i] for i in sorted(hr.choice(len(pool), size=R - 1, replace=False))]
+    assert len(bounds) == R - 1
+    smap = E.RangeMap.from_segments(bounds, paths, seg_lists, [cap] * S, engine=eng)
+    assert smap.max_list == 4 * cap
+    pair_cap = n * smap.max_list
+    with torch.cuda.stream(stream):
+        g = torch.Generator(device=dev)
+        g.manual_seed(7)
+        keys = torch.randint(0, 256, (n, 24), device=dev, generator=g, dtype=torch.uint8).contiguous()
+        outs = [(torch.zeros(n, dtype=torch.int32, device=dev), torch.zeros(n + 1, dtype=torch.int64, device=dev),
+                 torch.zeros(pair_cap, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int64, device=dev))
+                for _ in range(2)]
+        scratch = torch.zeros(E.range_route_scratch_bytes(n) // 8, dtype=torch.int64, device=dev)
+    stream.synchronize()
+
+    def route(h, out):
+        E._check(L.rf_amd_range_map_route_keys(h, keys.data_ptr(), 24, n, out[0].data_ptr(), out[1].data_ptr(),
+                                               out[2].data_ptr(), pair_cap, out[3].data_ptr(), scratch.data_ptr(), st))
+
+    def flat_arrays(lists):
+        """the rebuilt flat table in the C call's form: what the host holds before the timed region"""
+        rows = E.range_segment_lists(paths, lists)
+        loff = np.zeros(R + 1, dtype=np.uint64)
+        np.cumsum(np.array([len(x) for x in rows], dtype=np.uint64), out=loff[1:])
+        return rows, np.fromiter((i for x in rows for i in x), dtype=np.uint32, count=int(loff[-1])), loff
+
+    boff = np.zeros(R, dtype=np.uint64)
+    np.cumsum(np.array([len(b) for b in bounds], dtype=np.uint64), out=boff[1:])
+    bbytes = np.frombuffer(b"".join(bounds) + b"\0", dtype=np.uint8)
+    # the change: root segment 0 alternates between two lists of different lengths
+    root = [seg_lists[0], hr.integers(0, 1024, size=cap if len(seg_lists[0]) < cap else 1).tolist()]
+    tables = []
+    for x in root:
+        rows, flat, loff = flat_arrays([x] + seg_lists[1:])
+        tables.append((rows, flat, loff))
+    seg0 = np.zeros(1, dtype=np.uint32)
+    upd = [(np.array(x, dtype=np.uint32), np.array([0, len(x)], dtype=np.uint64)) for x in root]
+    hflat = ctypes.c_void_p()
+
+    def way_update(k):
+        E._check(L.rf_amd_range_map_update_segments(smap.h, seg0.ctypes.data, upd[k][0].ctypes.data,
+                                                    upd[k][1].ctypes.data, 1, st))
+
+    def create_flat(k):
+        E._check(L.rf_amd_range_map_create(eng.h, R, bbytes.ctypes.data, boff.ctypes.data, tables[k][1].ctypes.data,
+                                           tables[k][2].ctypes.data, ctypes.byref(hflat)))
+
+    def way_rebuild(k):
+        old = ctypes.c_void_p(hflat.value)
+        create_flat(k)
+        E._check(L.rf_amd_range_map_destroy_on(old, st))
+
+    # both ways' route output after the same change, compared before anything is timed
+    create_flat(0)
+    for k in (1, 0):
+        way_update(k)
+        way_rebuild(k)
+        route(smap.h, outs[0])
+        route(hflat, outs[1])
+        stream.synchronize()
+        m = int(outs[0][3].item())
+        assert m == int(outs[1][3].item()) and torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
+        assert torch.equal(outs[0][2][:m], outs[1][2][:m]), "the two ways' ids differ"
+    sample = hr.choice(n, size=1 << 14, replace=False)
+    hk = keys[torch.from_numpy(sample).to(dev)].cpu().numpy()
+    mirror = E.range_route_host(bounds, tables[0][0], [bytes(x) for x in hk])[0]
+    assert np.array_equal(mirror, outs[0][0].cpu().numpy().view(np.uint32)[sample]), "ranges differ from the host mirror"
+
+    def timed_change(way, k):
+        """(host microseconds of the C call or calls, HIP-event milliseconds around them on the stream)"""
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(stream)
+        t0 = time.perf_counter()
+        way(k)
+        host = time.perf_counter() - t0
+        b.record(stream)
+        stream.synchronize()
+        return host * 1e6, a.elapsed_time(b)
+
+    def timed_route(h):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(stream)
+        route(h, outs[0])
+        b.record(stream)
+        stream.synchronize()
+        return a.elapsed_time(b)
+
+    def timed_python_rebuild(k, old):
+        """the same rebuild through the Python class, its flattening of the rows included"""
+        stream.synchronize()
+        t0 = time.perf_counter()
+        new = E.RangeMap(bounds, tables[k][0], engine=eng)
+        old.close_on(st)
+        return (time.perf_counter() - t0) * 1e6, new
+
+    def rng(v):
+        return {"min": round(min(v), 4), "max": round(max(v), 4), "rounds": [round(x, 4) for x in v]}
+
+    t = {k: [] for k in ("update_host_us", "update_event_ms", "rebuild_host_us", "rebuild_event_ms",
+                         "rebuild_python_us", "route_segmented_before_ms", "route_segmented_after_ms", "route_flat_ms")}
+    pymap = E.RangeMap(bounds, tables[0][0], engine=eng)
+    for r in range(args.warmup + args.rounds):
+        k = 1 - r % 2
+        before = timed_route(smap.h)
+        uh, ue = timed_change(way_update, k)
+        after = timed_route(smap.h)
+        rh, re = timed_change(way_rebuild, k)
+        flat_ms = timed_route(hflat)
+        pu, pymap = timed_python_rebuild(k, pymap)
+        if r >= args.warmup:
+            for name, v in (("update_host_us", uh), ("update_event_ms", ue), ("rebuild_host_us", rh),
+                            ("rebuild_event_ms", re), ("rebuild_python_us", pu), ("route_segmented_before_ms", before),
+                            ("route_segmented_after_ms", after), ("route_flat_ms", flat_ms)):
+                t[name].append(v)
+    uh, rh = t["update_host_us"], t["rebuild_host_us"]
+    seg_route = t["route_segmented_before_ms"] + t["route_segmented_after_ms"]
+    out = {
+        "what": ("one root segment of a trunk-shaped range map changes (R leaves, paths of 4 segments, fan-out 16 per "
+                 "level, lists of 1 to 8 ids, capacity 8), two ways on one stream: (a) "
+                 "rf_amd_range_map_update_segments of that segment (scatter + flatten), (b) what a flat map needs: "
+                 "rf_amd_range_map_create of the rebuilt flat table + rf_amd_range_map_destroy_on of the old map. "
+                 "host_us: wall time of the C call or calls, their arrays built beforehand (the host's rebuild of the "
+                 "flat table is not in it); event_ms: HIP events on the stream around the calls, the stream idle at "
+                 "the first, so it contains the host time. rebuild_python_us: E.RangeMap(...) + close_on by the wall "
+                 "clock, the class's flattening of the rows included. route_*: one rf_amd_range_map_route_keys of n "
+                 "24-byte keys by events, on the segmented map before and after each update and on the flat map; "
+                 "the route kernels and the flat map are the parent commit's, so route_flat_ms is the parent's route "
+                 "call in this session. Alternating rounds in one process"),
+        "config": {"ranges": R, "segments": S, "fan_out": fan, "path_segments": 4, "capacity": cap, "n": n,
+                   "key_len": 24, "rounds": args.rounds, "warmup": args.warmup,
+                   "update_launches": 4, "ids_per_update_launch": E.diag_range_seg_launch_ids()},
+        **{k: rng(v) for k, v in t.items()},
+        "update_vs_rebuild_host": {"ranges_touch": not (max(uh) < min(rh) or max(rh) < min(uh)),
+                                   "update_faster_beyond_ranges": bool(max(uh) < min(rh))},
+        "update_vs_rebuild_event": {"update_faster_beyond_ranges": bool(max(t["update_event_ms"]) <
+                                                                        min(t["rebuild_event_ms"]))},
+        "route_segmented_within_flat_range": bool(min(t["route_flat_ms"]) <= max(seg_route) and
+                                                  min(seg_route) <= max(t["route_flat_ms"])),
+        "verified": ("after each change both ways' route output equal (ranges, offsets, ids, total) over all n keys; "
+                     "ranges equal E.range_route_host on 2^14 keys"),
+        "device": torch.cuda.get_device_name(0),
+    }
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as fh:
+        json.dump(out, fh, indent=1)
+        fh.write("\n")
+    print(json.dumps(out))
+    L.rf_amd_range_map_destroy(hflat)
+    pymap.close()
+    smap.close()
+    eng.close()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--filters", type=int, default=64)
@@ -516,16 +708,21 @@ def main():
                     help="route + ragged probe + compaction from raw keys through a range map")
     ap.add_argument("--update", action="store_true",
                     help="member updates of a resident set against destroy + create of the whole set")
+    ap.add_argument("--segments", action="store_true",
+                    help="a segment update of a range map against the rebuild of a flat one")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
         name = "multiget" + ("_var" if args.var else "") + ("_ragged" if args.ragged else "") + \
             ("_routed" if args.routed else "") + ".json"
-        args.out = os.path.join(ROOT, "profiles", "multiget_update.json" if args.update else name)
+        name = "multiget_update.json" if args.update else "range_segments.json" if args.segments else name
+        args.out = os.path.join(ROOT, "profiles", name)
     if not torch.cuda.is_available():
         sys.exit("multiget.py measures on the GPU: no HIP device")
     if args.update:
         return update_mode(args)
+    if args.segments:
+        return segments_mode(args)
     F, nk, n, Kf = args.filters, args.keys, args.n, args.k
     assert 1 <= F <= 64, "one value per filter: at most 64 filters"
     dev = torch.device("cuda:0")
