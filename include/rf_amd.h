@@ -313,6 +313,44 @@ uint64_t rf_amd_found_compact_scratch_bytes(uint64_t m);
 int rf_amd_found_compact(rf_amd_engine *e, const uint64_t *d_found, uint64_t m,
                          uint64_t *d_cand, uint64_t cap, uint64_t *d_count,
                          void *d_scratch, void *stream);
+/* the key-aware compaction: the step between a fan-out probe and the loop that consumes its
+ * candidates (trunk_ondisk_bundle_merge_lookup, src/trunk.c:6057-6087: key by key, bundle by
+ * bundle, newest first, bndl->branches[idx] per found value, out at the first definitive hit,
+ * :6085). The same words as rf_amd_found_compact, in the same order, but a record names its
+ * member instead of its pair, and the records come with a CSR over the keys.
+ * Fixed form: the words of rf_amd_filter_set_probe_{keys,var_keys,hashes}; the pair of (key i,
+ * slot j) is i * K + j, and its member id is d_member[i * K + j], or the slot j with d_member ==
+ * NULL. K need not equal any set's size: the call takes no set. Ragged form: the words of
+ * rf_amd_filter_set_probe_*_ragged with the same d_found pointer, the same d_member and the same
+ * n + 1 offsets: d_found and d_member are indexed by the absolute pair p, d_member_off[0] need not
+ * be 0, and nothing outside [d_member_off[0], d_member_off[n]) is read of either. One key's list
+ * holds at most 65,535 ids (the probe's limit; longer lists are not detected).
+ * d_key_off receives n + 1 uint64, d_key_off[0] = 0; key i owns the candidates
+ * [d_key_off[i], d_key_off[i+1]), and *d_count = d_key_off[n] = the total. Offsets and total are
+ * always the true values, also when they exceed cap. d_cand[j] = (uint64_t)member_id << 8 | value
+ * for j < min(total, cap); nothing is written at or past d_cand[cap) (cap == 0: d_cand may be
+ * NULL). The order is exactly rf_amd_found_compact's over the same words -- pair ascending, value
+ * descending within a word (routing_filter_get_next_value, src/routing_filter.h:94-105) -- so
+ * record j here and record j there describe the same (pair, value), and a key's candidates are
+ * contiguous and in list order: the trunk's newest-first path order. member_id is d_member[pair]
+ * as stored, all 32 bits, not validated (an id that finds nothing has word 0 and makes no
+ * record). d_cand_key is optional (NULL: not written): d_cand_key[j] = the key index i of record
+ * j, under the same cap rule.
+ * Asynchronous on stream (NULL = the engine's), three launches whatever n is, no allocation, no
+ * synchronisation, no atomics on global memory; the same input gives the same bytes. d_scratch
+ * (8-byte aligned) holds rf_amd_found_per_key_scratch_bytes(n) bytes (callable without a device;
+ * non-decreasing in n; a multiple of 8). n == 0 is OK: it writes d_key_off[0] = 0 and
+ * *d_count = 0 and nothing else. EINVAL: a NULL engine, n >= 2^56, a NULL d_key_off or d_count, a
+ * NULL d_cand with cap > 0; in the fixed form K == 0, K > 65,535 and n * K >= 2^56; with n > 0 a
+ * NULL d_found or d_scratch, and in the ragged form a NULL d_member or d_member_off. */
+uint64_t rf_amd_found_per_key_scratch_bytes(uint64_t n);
+int rf_amd_found_per_key(rf_amd_engine *e, const uint64_t *d_found, const uint32_t *d_member, uint32_t K,
+                         uint64_t n, uint64_t *d_key_off, uint64_t *d_cand, uint64_t *d_cand_key,
+                         uint64_t cap, uint64_t *d_count, void *d_scratch, void *stream);
+int rf_amd_found_per_key_ragged(rf_amd_engine *e, const uint64_t *d_found, const uint32_t *d_member,
+                                const uint64_t *d_member_off, uint64_t n, uint64_t *d_key_off,
+                                uint64_t *d_cand, uint64_t *d_cand_key, uint64_t cap, uint64_t *d_count,
+                                void *d_scratch, void *stream);
 /* ---- range maps: multi-get keys routed to their member lists on the device ----------------
  * What produces the ragged probe's per-key lists. At each node on its trunk path a key takes
  * the last pivot whose key is <= it (trunk_ondisk_node_find_pivot, src/trunk.c:5886-5932,

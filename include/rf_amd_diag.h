@@ -116,6 +116,9 @@ uint32_t rf_amd_diag_range_seg_launch_ids(void);
 /* the flatten expands a range's list of at most this many ids by one thread and a longer one by
  * a wave: a test takes lists of exactly this length and of one id more */
 uint32_t rf_amd_diag_range_seg_thread_ids(void);
+/* the keys of one tile of rf_amd_found_per_key / _ragged (the unit of their scratch and of their
+ * grid-stride loops, which honour rf_amd_diag_fanout_max_blocks like the route kernels) */
+uint32_t rf_amd_diag_per_key_tile(void);
 
 /* the source id the library was built from (16 hex digits of SHA-256 over the engine's
  * sources and headers, splinterdb_amd/build.py source_id): the Python loader refuses a

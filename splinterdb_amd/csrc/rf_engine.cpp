@@ -2264,6 +2264,7 @@ extern "C" int rf_amd_filter_set_probe_hashes_ragged(rf_amd_filter_set* s, const
 extern "C" int rf_amd_diag_fanout_max_blocks(uint32_t blocks) {
   rf_fanout_set_max_blocks(blocks);
   rf_range_set_max_blocks(blocks);
+  rf_per_key_set_max_blocks(blocks);
   return 0;
 }
 
@@ -2284,6 +2285,38 @@ extern "C" int rf_amd_found_compact(rf_amd_engine* e, const uint64_t* d_found, u
   (void)hipGetLastError();
   return launch_rc("compaction",
                    rf_launch_found_compact(stream_of(e, stream), d_found, m, d_cand, cap, d_count, d_scratch));
+}
+
+// ---- key-aware compaction: candidates with member ids and a CSR over the keys -----------------
+// The sizing and the argument checks are rf_per_key_plan.h's, the kernels rf_per_key.hip's.
+extern "C" uint64_t rf_amd_found_per_key_scratch_bytes(uint64_t n) { return per_key_scratch_bytes(n); }
+extern "C" uint32_t rf_amd_diag_per_key_tile(void) { return PER_KEY_TILE; }
+
+static int found_per_key(rf_amd_engine* e, bool ragged, const uint64_t* d_found, const uint32_t* d_member,
+                         const uint64_t* d_member_off, uint32_t K, uint64_t n, uint64_t* d_key_off, uint64_t* d_cand,
+                         uint64_t* d_cand_key, uint64_t cap, uint64_t* d_count, void* d_scratch, void* stream) {
+  if (const char* m = per_key_refusal(ragged, e, d_found, d_member, d_member_off, K, n, d_key_off, d_cand, cap,
+                                      d_count, d_scratch))
+    return fail(RF_AMD_EINVAL, m);
+  HIPCHK(hipSetDevice(e->device));
+  (void)hipGetLastError();
+  return launch_rc("per-key compaction",
+                   rf_launch_found_per_key(stream_of(e, stream), d_found, d_member, d_member_off, K, n, d_key_off,
+                                           d_cand, d_cand_key, cap, d_count, d_scratch));
+}
+
+extern "C" int rf_amd_found_per_key(rf_amd_engine* e, const uint64_t* d_found, const uint32_t* d_member, uint32_t K,
+                                    uint64_t n, uint64_t* d_key_off, uint64_t* d_cand, uint64_t* d_cand_key,
+                                    uint64_t cap, uint64_t* d_count, void* d_scratch, void* stream) {
+  return found_per_key(e, false, d_found, d_member, nullptr, K, n, d_key_off, d_cand, d_cand_key, cap, d_count,
+                       d_scratch, stream);
+}
+extern "C" int rf_amd_found_per_key_ragged(rf_amd_engine* e, const uint64_t* d_found, const uint32_t* d_member,
+                                           const uint64_t* d_member_off, uint64_t n, uint64_t* d_key_off,
+                                           uint64_t* d_cand, uint64_t* d_cand_key, uint64_t cap, uint64_t* d_count,
+                                           void* d_scratch, void* stream) {
+  return found_per_key(e, true, d_found, d_member, d_member_off, 0, n, d_key_off, d_cand, d_cand_key, cap, d_count,
+                       d_scratch, stream);
 }
 
 // ---- range maps: multi-get keys routed to their member lists --------------------------------

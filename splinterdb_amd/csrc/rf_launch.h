@@ -7,6 +7,7 @@
 #include "rf_plan.h"
 #include "rf_range_plan.h"
 #include "rf_range_seg_plan.h"
+#include "rf_per_key_plan.h"
 
 extern "C" {
 
@@ -92,6 +93,21 @@ int rf_launch_range_seg_flatten(void* stream, const rf::RangeSegDev* d);
 // diagnostics (rf_amd_diag_fanout_max_blocks): a cap on the route and flatten kernels' grids; 0 =
 // none
 void rf_range_set_max_blocks(uint32_t blocks);
+// k_range_scan alone, one workgroup: the exclusive scan of ntiles 32-bit tile sums into 64-bit
+// offsets off[ntiles], the total to *total and to *total_too (ntiles == 0: both 0)
+void rf_launch_range_scan(void* stream, const uint32_t* cnt, uint64_t ntiles, uint64_t* off, uint64_t* total,
+                          uint64_t* total_too);
+
+// ---- key-aware compaction (rf_per_key.hip) ---------------------------------------------------
+// k_per_key_count, k_range_scan, k_per_key_emit: the found words of n keys' pairs (moff: the
+// n + 1 pair offsets of the ragged form; nullptr: K pairs per key, member == nullptr: id = slot)
+// to key_off[n + 1], cand[< cap], cand_key[< cap] (nullptr: not written) and *count; scratch:
+// per_key_scratch_bytes(n) bytes, 8-byte aligned (rf_per_key_plan.h)
+int rf_launch_found_per_key(void* stream, const uint64_t* found, const uint32_t* member, const uint64_t* moff,
+                            uint32_t K, uint64_t n, uint64_t* key_off, uint64_t* cand, uint64_t* cand_key,
+                            uint64_t cap, uint64_t* count, void* scratch);
+// diagnostics (rf_amd_diag_fanout_max_blocks): a cap on both kernels' grids; 0 = none
+void rf_per_key_set_max_blocks(uint32_t blocks);
 
 // ---- estimate, hashing, routing, verify ---------------------------------------------------
 // bitmap (zeroed by the caller, bitmap_words a multiple of 4) -> counters[0] = entries

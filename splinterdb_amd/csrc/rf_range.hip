@@ -365,6 +365,12 @@ extern "C" void rf_range_set_max_blocks(uint32_t blocks) {
   g_range_max_blocks.store(blocks, std::memory_order_relaxed);
 }
 
+// k_range_scan on its own: the key-aware compaction (rf_per_key.hip) scans its tile sums with it
+extern "C" void rf_launch_range_scan(void* stream, const uint32_t* cnt, uint64_t ntiles, uint64_t* off,
+                                     uint64_t* total, uint64_t* total_too) {
+  hipLaunchKernelGGL(k_range_scan, dim3(1), dim3(1024), 0, (hipStream_t)stream, cnt, ntiles, off, total, total_too);
+}
+
 extern "C" int rf_launch_range_seg_scatter(void* stream, const rf::RangeSegUpdate* a) {
   if (a->npieces == 0) return 0;
   if (a->npieces > RANGE_SEG_WORDS / RANGE_SEG_PIECE_WORDS) return (int)hipErrorInvalidValue;
@@ -380,8 +386,7 @@ extern "C" int rf_launch_range_seg_flatten(void* stream, const rf::RangeSegDev* 
   if (cap && nblk > cap) nblk = cap;
   const dim3 g((uint32_t)nblk), b(RG_NT);
   hipLaunchKernelGGL(k_range_seg_len, g, b, 0, st, *d, ntiles);
-  hipLaunchKernelGGL(k_range_scan, dim3(1), dim3(1024), 0, st, d->tcnt, ntiles, d->toff, d->toff + ntiles,
-                     d->loff + d->num_ranges);
+  rf_launch_range_scan(st, d->tcnt, ntiles, d->toff, d->toff + ntiles, d->loff + d->num_ranges);
   hipLaunchKernelGGL(k_range_seg_emit, g, b, 0, st, *d, ntiles);
   return launch_status();
 }
@@ -406,7 +411,7 @@ extern "C" int rf_launch_range_route(void* stream, int var, const uint8_t* keys,
     else { if (lds) L(false, true); else L(false, false); }
 #undef L
   }
-  hipLaunchKernelGGL(k_range_scan, dim3(1), dim3(1024), 0, st, cnt, ntiles, toff, total, member_off + n);
+  rf_launch_range_scan(st, cnt, ntiles, toff, total, member_off + n);
   if (ntiles)
     hipLaunchKernelGGL(k_range_emit, g, b, 0, st, range, n, ntiles, toff, m->loff, m->list, member_off, member,
                        pair_cap);

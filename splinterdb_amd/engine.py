@@ -73,6 +73,8 @@ EXPORTED = [
     "rf_amd_diag_range_tile", "rf_amd_diag_range_lds_ranges",
     "rf_amd_range_map_create_segments", "rf_amd_range_map_num_segments", "rf_amd_range_map_update_segments",
     "rf_amd_diag_range_seg_launch_ids", "rf_amd_diag_range_seg_thread_ids",
+    "rf_amd_found_per_key_scratch_bytes", "rf_amd_found_per_key", "rf_amd_found_per_key_ragged",
+    "rf_amd_diag_per_key_tile",
 ]
 ROUTE_MAX_WORLD = 16
 FOUND_COMPACT_TILE = 4096  # found words per workgroup of rf_amd_found_compact (FC_TILE)
@@ -294,6 +296,12 @@ def load_library(build_if_missing=True):
     L.rf_amd_diag_range_seg_launch_ids.restype = u32
     L.rf_amd_diag_range_seg_thread_ids.argtypes = []
     L.rf_amd_diag_range_seg_thread_ids.restype = u32
+    L.rf_amd_found_per_key_scratch_bytes.argtypes = [u64]
+    L.rf_amd_found_per_key_scratch_bytes.restype = u64
+    L.rf_amd_found_per_key.argtypes = [vp, vp, vp, u32, u64, vp, vp, vp, u64, vp, vp, vp]
+    L.rf_amd_found_per_key_ragged.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, u64, vp, vp, vp]
+    L.rf_amd_diag_per_key_tile.argtypes = []
+    L.rf_amd_diag_per_key_tile.restype = u32
     L.rf_amd_host_alloc.argtypes = [vp, u64, ctypes.POINTER(vp)]
     L.rf_amd_host_free.argtypes = [vp, vp]
     L.rf_amd_host_free.restype = None
@@ -998,6 +1006,80 @@ def found_compact(d_found, m, d_cand, d_count, stream=None, engine=None):
     _compact_scratch[(id(eng), st)] = scratch
 
 
+def found_per_key_host(found, member, member_off):
+    """Host mirror of rf_amd_found_per_key_ragged: found and member indexed by the absolute pair,
+    member_off the n + 1 non-decreasing pair offsets (member_off[0] any value). Returns (key_off
+    uint64[n + 1], cand uint64[total], cand_key int64[total]): cand = member id << 8 | value in
+    found_candidates' order over the pairs [member_off[0], member_off[n]), key i owning
+    cand[key_off[i] : key_off[i + 1]], cand_key the key of every record."""
+    off = np.ascontiguousarray(member_off).reshape(-1).view(np.uint64).astype(np.int64)
+    first, last = int(off[0]), int(off[-1])
+    rec = found_candidates(np.ascontiguousarray(found).reshape(-1).view(np.uint64)[first:last])
+    pair = (rec >> np.uint64(8)).astype(np.int64)
+    ids = np.ascontiguousarray(member).reshape(-1).view(np.uint32)[first:last].astype(np.uint64)
+    cand = (ids[pair] << np.uint64(8)) | (rec & np.uint64(0xFF))
+    cand_key = ragged_pair_keys(off, pair)
+    key_off = np.zeros(off.size, dtype=np.uint64)
+    np.cumsum(np.bincount(cand_key, minlength=off.size - 1).astype(np.uint64), out=key_off[1:])
+    return key_off, cand, cand_key
+
+
+def found_per_key_host_fixed(found, member, K):
+    """Host mirror of rf_amd_found_per_key: the pair of (key i, slot j) is i * K + j; member None:
+    the id is the slot. Returns what found_per_key_host does."""
+    w = np.ascontiguousarray(found).reshape(-1).view(np.uint64)
+    n = w.size // K
+    if member is None:
+        member = np.tile(np.arange(K, dtype=np.uint32), n)
+    return found_per_key_host(w, member, np.arange(n + 1, dtype=np.uint64) * np.uint64(K))
+
+
+def found_per_key_scratch_bytes(n) -> int:
+    return int(load_library().rf_amd_found_per_key_scratch_bytes(n))
+
+
+def diag_per_key_tile() -> int:
+    """keys per tile of found_per_key / found_per_key_ragged (rf_amd_diag_per_key_tile)"""
+    return int(load_library().rf_amd_diag_per_key_tile())
+
+
+_per_key_scratch = {}  # (engine, stream) -> the scratch of the last found_per_key issued there
+
+
+def _found_per_key(call, n, d_key_off, d_cand, d_cand_key, d_count, stream, engine):
+    import torch
+    eng = engine or default_engine()
+    st = _stream(stream)
+    scratch = torch.empty(found_per_key_scratch_bytes(n) // 8, dtype=torch.int64, device=d_count.device)
+    cap = 0 if d_cand is None else d_cand.numel()
+    if d_cand_key is not None and d_cand_key.numel() < cap:
+        raise ValueError("d_cand_key is shorter than d_cand")
+    _check(call(eng.h, n, _dptr(d_key_off), _dptr(d_cand), _dptr(d_cand_key), cap, _dptr(d_count),
+                scratch.data_ptr(), st))
+    _per_key_scratch[(id(eng), st)] = scratch
+
+
+def found_per_key(d_found, d_member, K, n, d_key_off, d_cand, d_cand_key, d_count, stream=None, engine=None):
+    """rf_amd_found_per_key: the words d_found[:n * K] of a fixed-K probe to d_key_off (n + 1),
+    the records member id << 8 | value in d_cand (capacity: its length; None: offsets and count
+    only), their keys in d_cand_key (None: not written) and their total number in d_count,
+    asynchronously. d_member None: the id is the slot. The scratch is a torch buffer kept until
+    the next call on the same stream."""
+    L = load_library()
+    _found_per_key(lambda e, *a: L.rf_amd_found_per_key(e, _dptr(d_found), _dptr(d_member), K, *a),
+                   n, d_key_off, d_cand, d_cand_key, d_count, stream, engine)
+
+
+def found_per_key_ragged(d_found, d_member, d_member_off, n, d_key_off, d_cand, d_cand_key, d_count, stream=None,
+                         engine=None):
+    """rf_amd_found_per_key_ragged: found_per_key after a ragged probe, with the probe's d_found
+    (a tensor or the address the probe took), d_member and d_member_off"""
+    L = load_library()
+    _found_per_key(lambda e, *a: L.rf_amd_found_per_key_ragged(e, _dptr(d_found), _dptr(d_member),
+                                                               _dptr(d_member_off), *a),
+                   n, d_key_off, d_cand, d_cand_key, d_count, stream, engine)
+
+
 def diag_fanout_max_blocks(blocks: int):
     """rf_amd_diag_fanout_max_blocks: cap the fan-out probe's grid (diagnostics, process-wide)
     so that every wave takes several 64-key chunks; 0 restores the default"""
@@ -1151,16 +1233,21 @@ class FilterSet:
                                      lambda d_found: self.probe_var_keys_ragged(d_bytes, d_offsets, d_member,
                                                                                 d_member_off, n, d_found, stream))
 
-    def _multiget_ragged(self, d_member_off, n, cap, stream, probe):
+    def _probe_ragged(self, d_member_off, n, probe):
+        """the found words of a ragged multi-get: (d_found, first pair, number of pairs)"""
         import torch
-        dev = d_member_off.device
         first, last = (int(x) for x in d_member_off[[0, n]].tolist()) if n else (0, 0)  # the one read
         m = last - first
         # the m words of the pairs alone: the probe indexes from d_member_off[0] and writes
         # nothing below it, so it takes the address that word 0 would have
-        d_found = torch.empty(m, dtype=torch.int64, device=dev)
+        d_found = torch.empty(m, dtype=torch.int64, device=d_member_off.device)
         if m:
             probe(d_found.data_ptr() - 8 * first)
+        return d_found, first, m
+
+    def _multiget_ragged(self, d_member_off, n, cap, stream, probe):
+        import torch
+        d_found, first, m = self._probe_ragged(d_member_off, n, probe)
         d_cand, count = self._compact_found(d_found, m, 1, max(1, n) if cap is None else cap, stream)
         d_key = torch.searchsorted(d_member_off[:n + 1].view(torch.int64), (d_cand[:count] >> 8) + first,
                                    right=True) - 1
@@ -1183,7 +1270,8 @@ class FilterSet:
             lambda d_member, d_off, d_found: self.probe_var_keys_ragged(d_bytes, d_offsets, d_member, d_off, n,
                                                                         d_found, stream))
 
-    def _multiget_routed(self, n, cap, stream, route, probe):
+    def _probe_routed(self, stream, route, probe):
+        """route and ragged probe of a routed multi-get: (d_found, d_member_off, d_member, pairs)"""
         import torch
         d_range, d_off, d_member, d_total = route()
         if stream is not None:  # a raw handle torch's own copy is not ordered with
@@ -1192,9 +1280,91 @@ class FilterSet:
         d_found = torch.empty(m, dtype=torch.int64, device=d_off.device)
         if m:
             probe(d_member, d_off, d_found)
+        return d_found, d_off, d_member, m
+
+    def _multiget_routed(self, n, cap, stream, route, probe):
+        import torch
+        d_found, d_off, d_member, m = self._probe_routed(stream, route, probe)
         d_cand, count = self._compact_found(d_found, m, 1, max(1, n) if cap is None else cap, stream)
         d_key = torch.searchsorted(d_off[:n + 1], d_cand[:count] >> 8, right=True) - 1
         return d_cand, count, d_key
+
+    # ---- the same probes with the key-aware compaction in the place of found_compact + searchsorted:
+    # (d_key_off int64[n + 1], d_cand, count, d_cand_key), the first `count` records of d_cand being
+    # member id << 8 | value, key i owning d_cand[d_key_off[i] : d_key_off[i + 1]] and d_cand_key[j]
+    # being the key of record j. cap as in multiget.
+    def multiget_per_key(self, d_keys, key_len, d_member, K, n, cap=None, stream=None):
+        """probe_keys + found_per_key (d_member None: every member, the id is the slot)"""
+        import torch
+        d_found = torch.empty(n * K, dtype=torch.int64, device=d_keys.device)
+        self.probe_keys(d_keys, key_len, d_member, K, n, d_found, stream)
+        return self._per_key_tail(n, cap, stream, d_found.device,
+                                  lambda *a: found_per_key(d_found, d_member, K, n, *a, stream, self.engine))
+
+    def multiget_var_per_key(self, d_bytes, d_offsets, d_member, K, n, cap=None, stream=None):
+        """multiget_per_key for variable-length keys"""
+        import torch
+        d_found = torch.empty(n * K, dtype=torch.int64, device=d_offsets.device)
+        self.probe_var_keys(d_bytes, d_offsets, d_member, K, n, d_found, stream)
+        return self._per_key_tail(n, cap, stream, d_found.device,
+                                  lambda *a: found_per_key(d_found, d_member, K, n, *a, stream, self.engine))
+
+    def multiget_ragged_per_key(self, d_keys, key_len, d_member, d_member_off, n, cap=None, stream=None):
+        """probe_keys_ragged + found_per_key_ragged"""
+        return self._per_key_ragged(d_member, d_member_off, n, cap, stream,
+                                    lambda d_found: self.probe_keys_ragged(d_keys, key_len, d_member, d_member_off,
+                                                                           n, d_found, stream))
+
+    def multiget_var_ragged_per_key(self, d_bytes, d_offsets, d_member, d_member_off, n, cap=None, stream=None):
+        """multiget_ragged_per_key for variable-length keys"""
+        return self._per_key_ragged(d_member, d_member_off, n, cap, stream,
+                                    lambda d_found: self.probe_var_keys_ragged(d_bytes, d_offsets, d_member,
+                                                                               d_member_off, n, d_found, stream))
+
+    def _per_key_ragged(self, d_member, d_member_off, n, cap, stream, probe):
+        d_found, first, m = self._probe_ragged(d_member_off, n, probe)
+        at = d_found.data_ptr() - 8 * first  # the probe's d_found: indexed by the absolute pair
+        return self._per_key_tail(n, cap, stream, d_found.device,
+                                  lambda *a: found_per_key_ragged(at, d_member, d_member_off, n, *a, stream,
+                                                                  self.engine))
+
+    def multiget_routed_per_key(self, range_map, d_keys, key_len, n, cap=None, stream=None):
+        """RangeMap.route_keys + probe_keys_ragged + found_per_key_ragged, from raw device keys"""
+        return self._per_key_routed(
+            n, cap, stream, lambda: range_map.route_keys(d_keys, key_len, n, stream=stream),
+            lambda d_member, d_off, d_found: self.probe_keys_ragged(d_keys, key_len, d_member, d_off, n, d_found,
+                                                                    stream))
+
+    def multiget_var_routed_per_key(self, range_map, d_bytes, d_offsets, n, cap=None, stream=None):
+        """multiget_routed_per_key for variable-length keys"""
+        return self._per_key_routed(
+            n, cap, stream, lambda: range_map.route_var_keys(d_bytes, d_offsets, n, stream=stream),
+            lambda d_member, d_off, d_found: self.probe_var_keys_ragged(d_bytes, d_offsets, d_member, d_off, n,
+                                                                        d_found, stream))
+
+    def _per_key_routed(self, n, cap, stream, route, probe):
+        d_found, d_off, d_member, m = self._probe_routed(stream, route, probe)
+        return self._per_key_tail(n, cap, stream, d_off.device,
+                                  lambda *a: found_per_key_ragged(d_found, d_member, d_off, n, *a, stream,
+                                                                  self.engine))
+
+    def _per_key_tail(self, n, cap, stream, dev, compact):
+        """the per-key multi-get's tail: compact(d_key_off, d_cand, d_cand_key, d_count) once, and
+        once more into larger buffers when the candidates outnumber cap (default: one per key)"""
+        import torch
+        d_count = torch.zeros(1, dtype=torch.int64, device=dev)
+        d_key_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        size = max(1, n) if cap is None else cap
+        while True:
+            d_cand = torch.empty(size, dtype=torch.int64, device=dev)
+            d_cand_key = torch.empty(size, dtype=torch.int64, device=dev)
+            compact(d_key_off, d_cand, d_cand_key, d_count)
+            if stream is not None:  # a raw handle torch's own copy is not ordered with
+                torch.cuda.ExternalStream(stream).synchronize()
+            count = int(d_count.item())
+            if count <= size:
+                return d_key_off, d_cand, count, d_cand_key
+            size = count
 
     def _compact_found(self, d_found, n, K, cap, stream):
         """the multi-get's tail: the candidates of d_found[:n * K] as (d_cand, count)"""

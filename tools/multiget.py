@@ -62,7 +62,18 @@ through E.RangeMap(...) + close_on. A route call of 2^20 24-byte keys is timed o
 before and after every update and on the flat map. Both ways' route output after the same change
 is compared over all keys before anything is timed. Default output: profiles/range_segments.json.
 
-    timeout -k 10 600 python tools/multiget.py [--var] [--ragged | --routed] [--filters 64] [--keys 1048576]
+--per-key: the step behind the probe, two ways, on the --ragged lists and on the CSR that a route
+call writes for a map of R = 4,096 ranges with such lists (with --var: variable-length keys). What a
+consumer of the candidates needs is each record's member id and key. (parent_path) what a caller had:
+rf_amd_found_compact, torch.searchsorted of the records' pairs over the n + 1 offsets, the gather
+d_member[pair]. (per_key) one rf_amd_found_per_key_ragged, which writes the CSR of the records over
+the keys as well. Both ways' records, keys, offsets and totals are compared before anything is
+timed; then alternating rounds with the same method. Reported per workload: each way's rounds,
+minimum, maximum and median, the parent path's round-to-round spread, and whether the new call's
+median is within that spread of the parent path's. Default output: profiles/multiget_per_key.json
+(profiles/multiget_var_per_key.json).
+
+    timeout -k 10 600 python tools/multiget.py [--var] [--ragged | --routed | --per-key] [--filters 64] [--keys 1048576]
                                                [--n 16777216] [--k 4] [--rounds 7] [--warmup 2]
                                                [--out profiles/multiget.json]
     timeout -k 10 300 python tools/multiget.py --update --filters 1024 --keys 4096
@@ -372,6 +383,150 @@ def routed(args, fset, eng, stream, kin, timed, rng):
         "device": torch.cuda.get_device_name(0),
     }
     rmap.close()
+    return out
+
+
+def per_key(args, fset, eng, stream, kin, timed, rng):
+    """--per-key: candidates with member ids, keys and a CSR over the keys, two ways, on the
+    --ragged lists and on the CSR of a route call; kin: the keys' arguments"""
+    import statistics
+
+    import numpy as np
+    F, n, R = args.filters, args.n, ROUTED_R
+    st = stream.cuda_stream
+    dev = kin[0].device
+    hr = np.random.default_rng(13)
+    probe_r = fset.probe_var_keys_ragged if args.var else fset.probe_keys_ragged
+
+    def geometric(size):
+        return np.minimum(KPAD, 1 + hr.geometric(1.0 / 3.0, size=size)).astype(np.int64)
+
+    def ragged_csr():
+        """the --ragged lists: key i has min(16, 1 + Geometric(1/3)) random members"""
+        off_h = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(geometric(n), out=off_h[1:])
+        with torch.cuda.stream(stream):
+            g = torch.Generator(device=dev)
+            g.manual_seed(9)
+            off = torch.from_numpy(off_h).to(dev)
+            member = torch.randint(0, F, (int(off_h[-1]),), device=dev, generator=g).to(torch.int32)
+        stream.synchronize()
+        return off, member, int(off_h[-1])
+
+    def routed_csr():
+        """the --routed lists: the CSR a route call writes for a map of R ranges cut by keys of the
+        population, each range with such a list"""
+        pick = torch.from_numpy(hr.choice(n, size=2 * R, replace=False)).to(dev)
+        with torch.cuda.stream(stream):
+            if args.var:
+                lo, hi = kin[1][pick].tolist(), kin[1][pick + 1].tolist()
+                keys = {bytes(kin[0][a:b].cpu().numpy()) for a, b in zip(lo, hi)}
+            else:
+                keys = {bytes(row) for row in kin[0].reshape(n, 24)[pick].cpu().numpy()}
+        bounds = sorted(keys)[:R - 1]
+        assert len(bounds) == R - 1, "too few distinct keys"
+        llen = geometric(R)
+        lists = [hr.integers(0, F, size=int(k)).tolist() for k in llen]
+        rmap = E.RangeMap(bounds, lists, engine=eng)
+        with torch.cuda.stream(stream):
+            route = rmap.route_var_keys if args.var else rmap.route_keys
+            _, d_off, d_member, d_total = route(*kin, n, stream=st)
+        stream.synchronize()
+        m = int(d_total.item())
+        with torch.cuda.stream(stream):
+            off, member = d_off.clone(), d_member[:m].clone()
+        stream.synchronize()
+        del d_off, d_member
+        rmap.close()
+        return off, member, m
+
+    def measure(off, member, m):
+        with torch.cuda.stream(stream):
+            found = torch.zeros(m, dtype=torch.int64, device=dev)
+            d_count = torch.zeros(1, dtype=torch.int64, device=dev)
+            probe_r(*kin, member, off, n, found, stream=st)
+            E.found_compact(found, m, None, d_count, stream=st, engine=eng)
+        stream.synchronize()
+        count = int(d_count.item())
+        with torch.cuda.stream(stream):
+            d_cand = torch.zeros(max(count, 1), dtype=torch.int64, device=dev)
+            d_cand2, d_cand_key = torch.zeros_like(d_cand), torch.zeros_like(d_cand)
+            d_key_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+            d_count2 = torch.zeros(1, dtype=torch.int64, device=dev)
+        stream.synchronize()
+        got = {}
+
+        def parent_path():  # what a caller had: the records, then each record's key and member id
+            E.found_compact(found, m, d_cand, d_count, stream=st, engine=eng)
+            pair = d_cand[:count] >> 8
+            got["key"] = torch.searchsorted(off, pair, right=True) - 1
+            got["id"] = member[pair]
+
+        def per_key_call():
+            E.found_per_key_ragged(found, member, off, n, d_key_off, d_cand2, d_cand_key, d_count2, stream=st,
+                                   engine=eng)
+
+        # both ways once, compared before anything is timed
+        with torch.cuda.stream(stream):
+            parent_path()
+            per_key_call()
+        stream.synchronize()
+        with torch.cuda.stream(stream):
+            assert int(d_count2.item()) == count == int(d_key_off[n].item()), "the totals differ"
+            want = (got["id"].to(torch.int64) & 0xFFFFFFFF) << 8 | (d_cand[:count] & 0xFF)
+            assert torch.equal(d_cand2[:count], want), "records differ from found_compact + gather"
+            assert torch.equal(d_cand_key[:count], got["key"]), "keys differ from found_compact + searchsorted"
+            starts = torch.searchsorted(got["key"], torch.arange(n + 1, device=dev))
+            assert torch.equal(d_key_off, starts), "offsets differ from the runs of the records' keys"
+            del want, starts
+        stream.synchronize()
+        ways = {"parent_path": parent_path, "per_key": per_key_call,
+                "found_compact_alone": lambda: E.found_compact(found, m, d_cand, d_count, stream=st, engine=eng)}
+        t = {w: [] for w in ways}
+        for r in range(args.warmup + args.rounds):
+            for w, fn in ways.items():  # alternating: one of each per round
+                ms = timed(fn)
+                if r >= args.warmup:
+                    t[w].append(ms)
+        a, b = t["parent_path"], t["per_key"]
+        spread = max(a) - min(a)
+        return {
+            "pairs": m, "mean_list": round(m / n, 4), "candidates": count,
+            "ms": {w: dict(rng(v), median=round(statistics.median(v), 4)) for w, v in t.items()},
+            "parent_spread_ms": round(spread, 4),
+            # the condition: the new call's median is not above the parent path's by more than that
+            # path's own round-to-round spread
+            "per_key_within_parent_spread": bool(statistics.median(b) <= statistics.median(a) + spread),
+            "ranges_touch": not (max(a) < min(b) or max(b) < min(a)),
+            "per_key_faster_beyond_ranges": bool(max(b) < min(a)),
+            "per_key_slower_beyond_ranges": bool(max(a) < min(b)),
+            # the new call: every word at most twice; per key its pair offset read, its count written and
+            # read and its record offset written; per record at most one id, the record and its key
+            "per_key_algorithmic_bytes": 16 * m + 24 * n + 20 * count,
+            # the parent path: every word twice and the record written; then per record the shift (8 + 8),
+            # the search (8 + 8, the offsets it visits not counted), the - 1 (8 + 8), the gather (8 + 4 + 4)
+            "parent_algorithmic_bytes": 16 * m + 72 * count,
+        }
+
+    out = {
+        "what": ("the candidates of a ragged multi-get of n %s with each record's member id and key, two ways: "
+                 "(parent_path) found_compact, torch.searchsorted of the records' pairs over the n + 1 offsets, the "
+                 "gather member[pair]; (per_key) one rf_amd_found_per_key_ragged, which also writes the CSR of the "
+                 "records over the keys; on the --ragged lists (min(16, 1 + Geometric(1/3)) random members of one "
+                 "batch of F filters per key) and on the CSR of a route call through a map of R such lists; "
+                 "alternating rounds in one process, HIP events on the launch stream"
+                 % ("variable-length keys (keys.var_keys, 8-100 B)" if args.var else "24-byte keys")),
+        "config": {"filters": F, "keys_per_filter": args.keys, "n": n, "ranges": R, "rounds": args.rounds,
+                   "warmup": args.warmup, "fingerprint_size": 26, "log_index_size": 8},
+    }
+    for name, csr in (("ragged", ragged_csr), ("routed", routed_csr)):
+        off, member, m = csr()
+        out[name] = measure(off, member, m)
+        del off, member
+    out["verified"] = ("before timing, on both workloads: totals equal; every record equal to member[pair] << 8 | value "
+                       "of found_compact's record; every record's key equal to searchsorted's; the offsets equal "
+                       "to the starts of the keys' runs")
+    out["device"] = torch.cuda.get_device_name(0)
     return out
 
 
@@ -706,6 +861,8 @@ def main():
     ap.add_argument("--ragged", action="store_true", help="per-key member lists: ragged against padded to K = 16")
     ap.add_argument("--routed", action="store_true",
                     help="route + ragged probe + compaction from raw keys through a range map")
+    ap.add_argument("--per-key", dest="per_key", action="store_true",
+                    help="rf_amd_found_per_key_ragged against found_compact + searchsorted + gather")
     ap.add_argument("--update", action="store_true",
                     help="member updates of a resident set against destroy + create of the whole set")
     ap.add_argument("--segments", action="store_true",
@@ -714,7 +871,7 @@ def main():
     args = ap.parse_args()
     if args.out is None:
         name = "multiget" + ("_var" if args.var else "") + ("_ragged" if args.ragged else "") + \
-            ("_routed" if args.routed else "") + ".json"
+            ("_routed" if args.routed else "") + ("_per_key" if args.per_key else "") + ".json"
         name = "multiget_update.json" if args.update else "range_segments.json" if args.segments else name
         args.out = os.path.join(ROOT, "profiles", name)
     if not torch.cuda.is_available():
@@ -796,10 +953,12 @@ def main():
     def rng(v):
         return {"min": round(min(v), 4), "max": round(max(v), 4), "rounds": [round(x, 4) for x in v]}
 
-    if args.ragged or args.routed:
+    if args.ragged or args.routed or args.per_key:
         del found_a, found_b, member
         kin = (d_bytes, d_offs) if args.var else (keys, 24)
-        if args.routed:
+        if args.per_key:
+            out = per_key(args, fset, eng, stream, kin, timed, rng)
+        elif args.routed:
             out = routed(args, fset, eng, stream, kin, timed, rng)
         else:
             out = ragged(args, fset, eng, stream, kin, own, mean_len, timed, rng)
