@@ -411,6 +411,23 @@ extern "C" int rf_debug_set_phase_buffer(uint64_t* d_buf, uint32_t kid) {
 #ifndef RF_SCAT_WPE
 #define RF_SCAT_WPE 4
 #endif
+__device__ __forceinline__ void keys24_issue_dma(const uint8_t* kb, v4u* sw, uint32_t lane);  // below, with the probe
+// The partition's key ring (k_hash_scatter): read the lane's 24-byte key at LDS address `key`
+// once at most VM of the wave's vector-memory operations are outstanding; ring_step first issues
+// the ranking atomic of the slot just hashed (s_off word at LDS address `cnt`), whose result is
+// valid when the statement ends.
+template <int VM>
+__device__ __forceinline__ void ring_read(uint64_t& x, uint64_t& y, uint64_t& z, uint32_t key) {
+  asm volatile("s_waitcnt vmcnt(%4)\n\tds_read_b64 %0, %3\n\tds_read_b64 %1, %3 offset:8\n\tds_read_b64 %2, %3 offset:16\n\t"
+               "s_waitcnt lgkmcnt(0)"
+               : "=&v"(x), "=&v"(y), "=&v"(z) : "v"(key), "n"(VM) : "memory");
+}
+template <int VM>
+__device__ __forceinline__ void ring_step(uint32_t& rank, uint64_t& x, uint64_t& y, uint64_t& z, uint32_t cnt, uint32_t key) {
+  asm volatile("ds_add_rtn_u32 %3, %5, %6\n\ts_waitcnt vmcnt(%7)\n\tds_read_b64 %0, %4\n\tds_read_b64 %1, %4 offset:8\n\t"
+               "ds_read_b64 %2, %4 offset:16\n\ts_waitcnt lgkmcnt(0)"
+               : "=&v"(x), "=&v"(y), "=&v"(z), "=&v"(rank) : "v"(key), "v"(cnt), "v"(1u), "n"(VM) : "memory");
+}
 // FL (32-bit incremental builds): the entries are written flagged new, (e << 1) | 1.
 // RUNS (chained batches): the tile's value and end come from its run (TileRuns).
 // P16 (fresh single-run builds whose K4 is k_cb_bitmap, which uses an entry's low 16 bits
@@ -474,6 +491,62 @@ __global__ __launch_bounds__(SCAT_NT) __attribute__((amdgpu_waves_per_eu(RF_SCAT
     vo0 = offs[P.key_first + start + j];
     vo1 = offs[P.key_first + start + j + 1];
   }
+  auto entry_of = [&](uint32_t h) -> uint32_t { return ((((h >> (32 - fp_size)) << P.vs) | value) << flag) | flag; };
+  bool piped = false;  // keys hashed and ranked by the LDS ring below (else: the register path)
+  if constexpr (X3) {
+    // Keys through LDS: the wave's 8 KiB slice of s_stage, free until the staging, holds a ring
+    // of RING key slots of 1,536 bytes, filled by LDS-DMA and hashed from there (lane l takes
+    // key l of the slot). Slot k + RING is requested once slot k has been read; no key lives in
+    // VGPRs. The counted waits leave the RING - 1 slots behind slot k in flight (two DMA
+    // instructions per slot). Full tiles whose first key is 16-byte aligned only: the others
+    // take the register path below, as the probe's fast path does.
+    constexpr int RING = 5;
+    static_assert(RING == 5 && PER >= RING && RING * 96 * 16 <= (TILE_KEYS / (SCAT_NT / WAVE)) * 4, "waits below; slice size");
+    const uint8_t* tb = static_cast<const uint8_t*>(in0) + (uint64_t)(P.key_first + start) * 24;
+    piped = count == (uint32_t)TILE_KEYS && ((uintptr_t)tb & 15) == 0;  // workgroup-uniform
+    if (piped) {
+      v4u* sw = reinterpret_cast<v4u*>(s_vwin);
+      const uint8_t* kb = tb + (threadIdx.x & ~(WAVE - 1)) * 24;
+#pragma unroll
+      for (int r = 0; r < RING; r++) keys24_issue_dma(kb + r * (SCAT_NT * 24), sw + r * 96, lane);
+      // The loop's LDS reads and ranking atomics are written as instructions: for an LDS access
+      // it can see, the compiler waits vmcnt(0) while any LDS-DMA is in flight, which drains the
+      // ring once per slot. One statement (ring_step) issues slot k's ranking atomic, waits for
+      // slot k + 1's DMA (this wave's own, so no barrier), reads slot k + 1 and waits for all of
+      // it: no register the compiler can touch is ever pending, and the atomic's latency runs
+      // under the DMA wait. VM = 2 * min(RING - 1, PER - 1 - slot): the DMA instructions of the
+      // slots behind the one read. The counts are written out for RING == 5; a VMEM instruction
+      // added inside the loop would only make them wait for more than they need, never less.
+      const uint32_t lds_key = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t*)reinterpret_cast<uint8_t*>(sw) + lane * 24;
+      const uint32_t lds_off = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t*)s_off;
+      uint64_t x, y, z;
+      auto key_at = [&](int k) -> uint32_t { return lds_key + (k % RING) * 1536; };
+      auto hash_slot = [&](int k) {  // x, y, z hold slot k, and every lane's reads of it are done
+        wave_sync_lds();
+        if (k + RING < PER) keys24_issue_dma(kb + (k + RING) * (SCAT_NT * 24), sw + (k % RING) * 96, lane);
+        const uint32_t w[6] = {(uint32_t)x, (uint32_t)(x >> 32), (uint32_t)y, (uint32_t)(y >> 32), (uint32_t)z, (uint32_t)(z >> 32)};
+        v[k] = entry_of(xxh32_24(w, seed));
+        return lds_off + cb_of(v[k]) * 4;
+      };
+      ring_read<8>(x, y, z, key_at(0));
+#pragma unroll
+      for (int k = 0; k < PER - RING; k++) {
+        const uint32_t ao = hash_slot(k);
+        ring_step<8>(rank[k], x, y, z, ao, key_at(k + 1));
+      }
+      uint32_t ao = hash_slot(PER - 5);
+      ring_step<6>(rank[PER - 5], x, y, z, ao, key_at(PER - 4));
+      ao = hash_slot(PER - 4);
+      ring_step<4>(rank[PER - 4], x, y, z, ao, key_at(PER - 3));
+      ao = hash_slot(PER - 3);
+      ring_step<2>(rank[PER - 3], x, y, z, ao, key_at(PER - 2));
+      ao = hash_slot(PER - 2);
+      ring_step<0>(rank[PER - 2], x, y, z, ao, key_at(PER - 1));
+      ao = hash_slot(PER - 1);
+      asm volatile("ds_add_rtn_u32 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=&v"(rank[PER - 1]) : "v"(ao), "v"(1u) : "memory");
+    }
+  }
+  if (!piped) {
 #pragma unroll
   for (int k0 = 0; k0 < PER; k0 += HASH_CHUNK) {
     if constexpr (X3) {
@@ -562,10 +635,13 @@ __global__ __launch_bounds__(SCAT_NT) __attribute__((amdgpu_waves_per_eu(RF_SCAT
                  : "v"(v[k0]), "v"(v[k0 + 1]), "v"(v[k0 + 2]), "v"(v[k0 + 3]), "v"(v[k0 + 4]),
                    "v"(v[k0 + 5]), "v"(v[k0 + 6]), "v"(v[k0 + 7]));
   }
-  DBG_PHASE_K(2, 5);  // thread 0's keys loaded and hashed (no barrier)
+  }
+  DBG_PHASE_K(2, 5);  // thread 0's keys loaded and hashed (no barrier); piped: and ranked
+  if (!piped) {
 #pragma unroll
-  for (int k = 0; k < PER; k++) {
-    if (key_of(k) < count) rank[k] = atomicAdd(&s_off[cb_of(v[k])], 1u);
+    for (int k = 0; k < PER; k++) {
+      if (key_of(k) < count) rank[k] = atomicAdd(&s_off[cb_of(v[k])], 1u);
+    }
   }
   __syncthreads();
   DBG_PHASE_K(2, 1);

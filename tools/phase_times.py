@@ -81,6 +81,8 @@ elif KID == 3:
              8: "line write"}
     order = [15, 0, 1, 2, 3, 4, 8]
 else:
+    # 24-byte keys through the LDS ring: thread 0's stamp 5 follows its last ranking atomic, so
+    # "load+hash" includes the ranking and "rank" is the wait for the slowest wave at the barrier
     names = {15: "entry", 0: "init", 5: "load+hash (thread 0)", 1: "rank", 2: "scan+reserve",
              3: "stage", 4: "slots", 8: "write runs"}
     order = [15, 0, 5, 1, 2, 3, 4, 8]
