@@ -191,6 +191,15 @@ int rf_amd_probe_many_hashes_host(rf_amd_engine *e, rf_amd_batch *const *batches
  * rf_amd_batch_trim of a member leaves the set valid (pages, slots and probe lines keep their
  * addresses). destroy synchronises the device, as rf_amd_batch_destroy does. */
 typedef struct rf_amd_filter_set rf_amd_filter_set;
+/* a bundle without a maplet that holds one branch: every key finds value 0 (found word 1)
+ * (trunk_ondisk_bundle_merge_lookup, src/trunk.c:6020-6022: found_values = num_branches == 1 ? 1
+ * : 0 without a filter call -- the bundles of memtable incorporations). Accepted wherever a set
+ * takes a member: batches[i] of rf_amd_filter_set_create, _create_cap and _update;
+ * filter_index[i] is ignored, as it is for NULL. A NULL batch stays the bundle with no branch.
+ * Such a member has no seed and takes no part in the seed rule of the keys forms; it counts for
+ * num_members. Downstream its word 1 is the record index << 8 | 0 of rf_amd_found_compact and
+ * member_id << 8 | 0 of rf_amd_found_per_key*, at the member's place in the key's list. */
+#define RF_AMD_MEMBER_UNFILTERED ((rf_amd_batch *)(uintptr_t)1)
 int  rf_amd_filter_set_create(rf_amd_engine *e, rf_amd_batch *const *batches,
                               const uint32_t *filter_index, uint32_t num_members,
                               rf_amd_filter_set **out);
@@ -296,6 +305,43 @@ int rf_amd_filter_set_probe_var_keys_ragged(rf_amd_filter_set *s, const uint8_t 
 int rf_amd_filter_set_probe_hashes_ragged(rf_amd_filter_set *s, const uint32_t *d_hashes,
                                           const uint32_t *d_member, const uint64_t *d_member_off,
                                           uint64_t n, uint64_t *d_found, void *stream);
+/* existence multi-get (SPLINTERDB_LOOKUP_MIGHT_EXIST, include/splinterdb/splinterdb.h:241,
+ * src/lookup_result.h:149-169): answered by the filters alone, the first found_values != 0
+ * ending the lookup (src/trunk.c:6036-6043, :6153-6158). The six probe calls with d_exists (n
+ * bytes, any alignment) in the place of d_found: d_exists[i] = the OR of the two bits below over
+ * key i's list -- its K members in the fixed forms, d_member[d_member_off[i] ..
+ * d_member_off[i+1]) in the ragged ones. 0: no bundle of the list can hold the key. Bit 0 set:
+ * the reference's existence lookup would stop at a filter hit, so the answer is "might exist"
+ * whatever else the list holds. 2 alone: the caller looks the key up in the list's unfiltered
+ * bundles. Every one of the n bytes is written, those of keys with empty lists too (0), and
+ * nothing outside [d_exists, d_exists + n); no found word is written. Everything else is the
+ * probe calls' contract: the member-id rules (an id >= num_members, a NULL member and a member
+ * whose build failed add nothing), the seed rule of the keys forms, d_member == NULL in the
+ * fixed forms meaning all members (K == num_members), d_member_off[0] any value, at most 65,535
+ * ids per list, asynchronous on stream (NULL = the engine's), one launch, no allocation, no
+ * synchronisation, n == 0 OK and touching nothing, and the same EINVAL cases with d_exists in
+ * d_found's place. */
+#define RF_AMD_EXISTS_FILTER_HIT 1u  /* some filter of the key's list found a value */
+#define RF_AMD_EXISTS_UNFILTERED 2u  /* the list holds an unfiltered member: its branch decides */
+int rf_amd_filter_set_exists_keys(rf_amd_filter_set *s, const void *d_keys, uint32_t key_len,
+                                  const uint32_t *d_member, uint32_t K, uint64_t n,
+                                  uint8_t *d_exists, void *stream);
+int rf_amd_filter_set_exists_var_keys(rf_amd_filter_set *s, const uint8_t *d_bytes,
+                                      const uint64_t *d_offsets, const uint32_t *d_member,
+                                      uint32_t K, uint64_t n, uint8_t *d_exists, void *stream);
+int rf_amd_filter_set_exists_hashes(rf_amd_filter_set *s, const uint32_t *d_hashes,
+                                    const uint32_t *d_member, uint32_t K, uint64_t n,
+                                    uint8_t *d_exists, void *stream);
+int rf_amd_filter_set_exists_keys_ragged(rf_amd_filter_set *s, const void *d_keys, uint32_t key_len,
+                                         const uint32_t *d_member, const uint64_t *d_member_off,
+                                         uint64_t n, uint8_t *d_exists, void *stream);
+int rf_amd_filter_set_exists_var_keys_ragged(rf_amd_filter_set *s, const uint8_t *d_bytes,
+                                             const uint64_t *d_offsets, const uint32_t *d_member,
+                                             const uint64_t *d_member_off, uint64_t n,
+                                             uint8_t *d_exists, void *stream);
+int rf_amd_filter_set_exists_hashes_ragged(rf_amd_filter_set *s, const uint32_t *d_hashes,
+                                           const uint32_t *d_member, const uint64_t *d_member_off,
+                                           uint64_t n, uint8_t *d_exists, void *stream);
 /* the set bits of m found_values words as an ordered candidate list: record =
  * index << 8 | value, index ascending, and within one word value DESCENDING (the order in
  * which routing_filter_get_next_value hands them out, src/routing_filter.h:94-105; with the

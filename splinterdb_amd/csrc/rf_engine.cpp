@@ -2039,7 +2039,7 @@ struct rf_amd_filter_set : SetState {
   DevBuf d_groups;
   // what a member update hands the planner and gets back, kept between calls
   std::vector<uint32_t> upd_seed;
-  std::vector<uint8_t> upd_null;
+  std::vector<uint8_t> upd_kind;  // SetMemberKind of every entry
   SetUpdatePlan upd_plan;
 };
 
@@ -2050,10 +2050,21 @@ static ProbeGroup null_group() {  // NULL_ROUTING_FILTER: finds nothing
   return g;
 }
 
-// a member named by a call: nullptr batch = NULL_ROUTING_FILTER, else a built batch of engine e
-// and one of its filters
+// RF_AMD_MEMBER_UNFILTERED (src/trunk.c:6020-6022): the NULL entry that finds value 0 for every key
+static ProbeGroup unfiltered_group() {
+  ProbeGroup g = null_group();
+  g.err |= GROUP_UNFILTERED;
+  return g;
+}
+
+static uint8_t member_kind(const rf_amd_batch* b) {
+  return !b ? SET_NULL : b == RF_AMD_MEMBER_UNFILTERED ? SET_UNFILTERED : SET_FILTER;
+}
+
+// a member named by a call: nullptr batch = NULL_ROUTING_FILTER, RF_AMD_MEMBER_UNFILTERED (neither
+// is dereferenced), else a built batch of engine e and one of its filters
 static int check_member(const rf_amd_engine* e, const rf_amd_batch* b, uint32_t f) {
-  if (!b) return 0;
+  if (member_kind(b) != SET_FILTER) return 0;
   if (!b->built || b->eng != e) return fail(RF_AMD_EINVAL, "member on an unbuilt or foreign batch");
   if (f >= b->F) return fail(RF_AMD_EINVAL, "bad filter index");
   return 0;
@@ -2075,26 +2086,27 @@ static int filter_set_create(rf_amd_engine* e, rf_amd_batch* const* batches, con
   // room for any later call of up to `capacity` entries: an update then allocates nothing on
   // the host either
   s->upd_seed.reserve(capacity);
-  s->upd_null.reserve(capacity);
+  s->upd_kind.reserve(capacity);
   s->upd_plan.order.reserve(capacity);
   s->upd_plan.cuts.reserve(capacity / SET_UPD_PER_LAUNCH + 2);
   s->upd_seed.assign(num_members, 0u);
-  s->upd_null.assign(num_members, 1);
+  s->upd_kind.assign(num_members, SET_NULL);
   for (uint32_t g = 0; g < num_members; g++) {
     ids[g] = g;
     rf_amd_batch* b = batches[g];
-    if (!b) continue;
+    s->upd_kind[g] = member_kind(b);
+    if (s->upd_kind[g] == SET_UNFILTERED) groups[g] = unfiltered_group();
+    if (s->upd_kind[g] != SET_FILTER) continue;
     const uint32_t f = filter_index ? filter_index[g] : 0u;
     if (int rc = check_member(e, b, f)) return rc;
     if (int rc = batch_errors(b)) return rc;
     groups[g] = probe_group_of(b, f);
     s->upd_seed[g] = b->cfg.seed;
-    s->upd_null[g] = 0;
   }
   // the members as one update of the empty set: its count and seed rule (the entries go up by
   // the copy below, not by launches)
   std::string msg;
-  if (int rc = plan_set_update(s.get(), num_members, ids.data(), s->upd_null.data(), s->upd_seed.data(),
+  if (int rc = plan_set_update(s.get(), num_members, ids.data(), s->upd_kind.data(), s->upd_seed.data(),
                                &s->upd_plan, &msg))
     return fail(rc, msg);
   if (s->d_groups.alloc(sizeof(ProbeGroup) * capacity, &e->pool)) return RF_AMD_ENOMEM;
@@ -2136,16 +2148,16 @@ extern "C" int rf_amd_filter_set_update(rf_amd_filter_set* s, const uint32_t* me
   if (count == 0) return 0;
   if (!member_id || !batches) return fail(RF_AMD_EINVAL, "null member arrays");
   s->upd_seed.resize(count);
-  s->upd_null.resize(count);
+  s->upd_kind.resize(count);
   for (uint32_t i = 0; i < count; i++) {
     const rf_amd_batch* b = batches[i];
     if (int rc = check_member(s->eng, b, filter_index ? filter_index[i] : 0u)) return rc;
-    s->upd_null[i] = b ? 0 : 1;
-    s->upd_seed[i] = b ? b->cfg.seed : 0u;
+    s->upd_kind[i] = member_kind(b);
+    s->upd_seed[i] = s->upd_kind[i] == SET_FILTER ? b->cfg.seed : 0u;
   }
   HIPCHK(hipSetDevice(s->eng->device));
   std::string msg;
-  if (int rc = plan_set_update(s, count, member_id, s->upd_null.data(), s->upd_seed.data(), &s->upd_plan, &msg))
+  if (int rc = plan_set_update(s, count, member_id, s->upd_kind.data(), s->upd_seed.data(), &s->upd_plan, &msg))
     return fail(rc, msg);
   (void)hipGetLastError();
   const SetUpdatePlan& plan = s->upd_plan;
@@ -2160,8 +2172,8 @@ extern "C" int rf_amd_filter_set_update(rf_amd_filter_set* s, const uint32_t* me
       rf_amd_batch* b = batches[i];
       en.id = member_id[i];
       en.pad = 0;
-      if (!b) {
-        en.g = null_group();
+      if (s->upd_kind[i] != SET_FILTER) {
+        en.g = s->upd_kind[i] == SET_UNFILTERED ? unfiltered_group() : null_group();
         en.out = nullptr;
         continue;
       }
@@ -2201,10 +2213,11 @@ extern "C" uint32_t rf_amd_filter_set_num_members(const rf_amd_filter_set* s) { 
 // The fixed form: key i against its K members (d_member == nullptr: all of them), d_member_off
 // nullptr. The ragged form: key i against d_member[d_member_off[i] .. d_member_off[i+1]), K
 // unused. `ragged` names the form, not d_member_off: a ragged call without offsets is refused
-// as one (after its n == 0 return), not as a fixed call with K == 0.
+// as one (after its n == 0 return), not as a fixed call with K == 0. `exists`: the existence
+// form of the same call, d_found then being the n bytes d_exists (rf_amd_filter_set_exists_*).
 static int set_probe(rf_amd_filter_set* s, int kind, const void* in0, const uint64_t* offs, uint32_t key_len,
                      const uint32_t* d_member, uint32_t K, const uint64_t* d_member_off, uint64_t n,
-                     uint64_t* d_found, void* stream, bool ragged) {
+                     void* d_found, void* stream, bool ragged, bool exists = false) {
   if (!s) return fail(RF_AMD_EINVAL, "null filter set");
   if (!ragged) {
     if (K == 0) return fail(RF_AMD_EINVAL, "K == 0");
@@ -2218,10 +2231,15 @@ static int set_probe(rf_amd_filter_set* s, int kind, const void* in0, const uint
     return fail(RF_AMD_EINVAL, "null probe buffer");
   HIPCHK(hipSetDevice(s->eng->device));
   (void)hipGetLastError();
+  if (exists)
+    return launch_rc(ragged ? "ragged existence probe" : "existence probe",
+                     rf_launch_probe_fanout_exists(stream_of(s->eng, stream), kind, in0, offs, key_len, s->seed,
+                                                   s->d_groups.as<ProbeGroup>(), s->num_members, d_member, K,
+                                                   d_member_off, n, static_cast<uint8_t*>(d_found)));
   return launch_rc(ragged ? "ragged fan-out probe" : "fan-out probe",
                    rf_launch_probe_fanout(stream_of(s->eng, stream), kind, in0, offs, key_len, s->seed,
                                           s->d_groups.as<ProbeGroup>(), s->num_members, d_member, K, d_member_off, n,
-                                          d_found));
+                                          static_cast<uint64_t*>(d_found)));
 }
 
 extern "C" int rf_amd_filter_set_probe_keys(rf_amd_filter_set* s, const void* d_keys, uint32_t key_len,
@@ -2259,6 +2277,45 @@ extern "C" int rf_amd_filter_set_probe_hashes_ragged(rf_amd_filter_set* s, const
                                                      const uint32_t* d_member, const uint64_t* d_member_off,
                                                      uint64_t n, uint64_t* d_found, void* stream) {
   return set_probe(s, IN_HASH, d_hashes, nullptr, 4, d_member, 0, d_member_off, n, d_found, stream, true);
+}
+
+// the existence forms: the same calls with the n bytes d_exists in d_found's place
+extern "C" int rf_amd_filter_set_exists_keys(rf_amd_filter_set* s, const void* d_keys, uint32_t key_len,
+                                             const uint32_t* d_member, uint32_t K, uint64_t n, uint8_t* d_exists,
+                                             void* stream) {
+  if (!s) return fail(RF_AMD_EINVAL, "null filter set");
+  if (key_len == 0) return fail(RF_AMD_EINVAL, "key_len 0");
+  return set_probe(s, fixed_kind(d_keys, key_len), d_keys, nullptr, key_len, d_member, K, nullptr, n, d_exists,
+                   stream, false, true);
+}
+extern "C" int rf_amd_filter_set_exists_var_keys(rf_amd_filter_set* s, const uint8_t* d_bytes,
+                                                 const uint64_t* d_offsets, const uint32_t* d_member, uint32_t K,
+                                                 uint64_t n, uint8_t* d_exists, void* stream) {
+  return set_probe(s, IN_VAR, d_bytes, d_offsets, 0, d_member, K, nullptr, n, d_exists, stream, false, true);
+}
+extern "C" int rf_amd_filter_set_exists_hashes(rf_amd_filter_set* s, const uint32_t* d_hashes,
+                                               const uint32_t* d_member, uint32_t K, uint64_t n, uint8_t* d_exists,
+                                               void* stream) {
+  return set_probe(s, IN_HASH, d_hashes, nullptr, 4, d_member, K, nullptr, n, d_exists, stream, false, true);
+}
+extern "C" int rf_amd_filter_set_exists_keys_ragged(rf_amd_filter_set* s, const void* d_keys, uint32_t key_len,
+                                                    const uint32_t* d_member, const uint64_t* d_member_off,
+                                                    uint64_t n, uint8_t* d_exists, void* stream) {
+  if (!s) return fail(RF_AMD_EINVAL, "null filter set");
+  if (key_len == 0) return fail(RF_AMD_EINVAL, "key_len 0");
+  return set_probe(s, fixed_kind(d_keys, key_len), d_keys, nullptr, key_len, d_member, 0, d_member_off, n, d_exists,
+                   stream, true, true);
+}
+extern "C" int rf_amd_filter_set_exists_var_keys_ragged(rf_amd_filter_set* s, const uint8_t* d_bytes,
+                                                        const uint64_t* d_offsets, const uint32_t* d_member,
+                                                        const uint64_t* d_member_off, uint64_t n, uint8_t* d_exists,
+                                                        void* stream) {
+  return set_probe(s, IN_VAR, d_bytes, d_offsets, 0, d_member, 0, d_member_off, n, d_exists, stream, true, true);
+}
+extern "C" int rf_amd_filter_set_exists_hashes_ragged(rf_amd_filter_set* s, const uint32_t* d_hashes,
+                                                      const uint32_t* d_member, const uint64_t* d_member_off,
+                                                      uint64_t n, uint8_t* d_exists, void* stream) {
+  return set_probe(s, IN_HASH, d_hashes, nullptr, 4, d_member, 0, d_member_off, n, d_exists, stream, true, true);
 }
 
 extern "C" int rf_amd_diag_fanout_max_blocks(uint32_t blocks) {

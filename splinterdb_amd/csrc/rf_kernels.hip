@@ -33,6 +33,7 @@
 #include <stdint.h>
 
 #include <atomic>
+#include <type_traits>
 
 #include "rf_device.h"
 #include "rf_plan.h"
@@ -4767,6 +4768,14 @@ __global__ __launch_bounds__(WAVE) void k_probe_small(SmallProbe a) {
 // line cannot answer (overflowed, none) takes probe_group, line and image walk, as
 // k_probe_groups does. member == nullptr: slot j is member j (K == ng), no id array is read.
 // The last, partial wave and the pairs past n K are masked.
+// A set's table also holds unfiltered members (GROUP_UNFILTERED, rf_plan.h): their word is 1,
+// nothing is read for them.
+// EXISTS (rf_amd_filter_set_exists_*, SPLINTERDB_LOOKUP_MIGHT_EXIST: src/trunk.c:6036-6043): the
+// same walk stores no found word. A pair of a filter whose word is not zero ORs
+// RF_AMD_EXISTS_FILTER_HIT, an unfiltered pair RF_AMD_EXISTS_UNFILTERED, into its key's word of
+// the wave's 64 in LDS (cleared per chunk, before the walk); after the walk lane k stores the
+// byte of key wf + k: one coalesced 64-byte store per wave, bytes only, so `found` (there the
+// n bytes d_exists) has any alignment, and every key's byte is written, pairs or none.
 constexpr int FAN_NT = 256;
 #ifndef RF_FAN_U
 #define RF_FAN_U 2
@@ -4822,12 +4831,25 @@ __device__ __forceinline__ uint32_t fan_hash_chunk(const void* __restrict__ in0,
   return h;
 }
 
-template <int KIND>
+// what a fan-out kernel writes: found words, or (EXISTS) one byte per key
+template <bool EXISTS>
+using fan_out_t = typename std::conditional<EXISTS, uint8_t, uint64_t>::type;
+
+// 0 nothing found, 1 probe line, 2 no lines or dense lines: probe_group, 3 unfiltered: word 1
+__device__ __forceinline__ uint32_t fan_state(uint32_t err, uint32_t px) {
+  return err ? (err & GROUP_UNFILTERED ? 3u : 0u) : ((px >> 24) - 1u < LINE_DENSE - 1u ? 1u : 2u);
+}
+// EXISTS: what a pair in state st with word r adds to its key's byte
+__device__ __forceinline__ uint32_t fan_exists_bits(uint32_t st, uint64_t r) {
+  return st == 3 ? RF_AMD_EXISTS_UNFILTERED : (r != 0 ? RF_AMD_EXISTS_FILTER_HIT : 0u);
+}
+
+template <int KIND, bool EXISTS>
 __global__ __launch_bounds__(FAN_NT) __attribute__((amdgpu_waves_per_eu(5))) void k_probe_fanout(const void* __restrict__ in0,
                                                          const uint64_t* __restrict__ offs, uint32_t key_len,
                                                          uint32_t seed, const ProbeGroup* __restrict__ groups,
                                                          uint32_t ng, const uint32_t* __restrict__ member,
-                                                         uint32_t K, uint64_t n, uint64_t* __restrict__ found) {
+                                                         uint32_t K, uint64_t n, fan_out_t<EXISTS>* __restrict__ found) {
   constexpr bool WAVE_KEYS = KIND == IN_KEYS24;
   constexpr bool WAVE_VAR = KIND == IN_VAR;
   constexpr int NW = FAN_NT / WAVE;
@@ -4835,6 +4857,7 @@ __global__ __launch_bounds__(FAN_NT) __attribute__((amdgpu_waves_per_eu(5))) voi
   constexpr uint32_t VCAP = FAN_VCAP;
   __shared__ __attribute__((aligned(16))) uint32_t s_vk[WAVE_VAR ? NW : 1][WAVE_VAR ? VCAP / 4 + 4 : 1];
   __shared__ uint32_t s_h[NW][WAVE];
+  __shared__ uint32_t s_ex[EXISTS ? NW : 1][EXISTS ? WAVE : 1];  // EXISTS: the bits of the wave's keys
   const uint32_t lane = threadIdx.x & (WAVE - 1);
   const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x) / WAVE;
   const uint64_t nwaves = (n + WAVE - 1) / WAVE;
@@ -4844,6 +4867,7 @@ __global__ __launch_bounds__(FAN_NT) __attribute__((amdgpu_waves_per_eu(5))) voi
     const uint32_t nk = (uint32_t)min<uint64_t>(WAVE, n - wf);
     const uint32_t h = fan_hash_chunk<KIND>(in0, offs, key_len, seed, wf, nk, lane, s_keys[wv], s_vk[wv]);
     s_h[wv][lane] = h;
+    if constexpr (EXISTS) s_ex[wv][lane] = 0;
     wave_sync_lds();
     const uint64_t pbase = wf * K;          // the wave's first pair (n K < 2^56)
     const uint64_t np = (uint64_t)nk * K;   // its pairs
@@ -4886,8 +4910,7 @@ __global__ __launch_bounds__(FAN_NT) __attribute__((amdgpu_waves_per_eu(5))) voi
           pf[u] = G->fpl;
           pl[u] = (uint64_t)(uintptr_t)G->lines;
         }
-        // 0 nothing found, 1 probe line, 2 no lines or dense lines: probe_group
-        st[u] = err ? 0u : ((px[u] >> 24) - 1u < LINE_DENSE - 1u ? 1u : 2u);
+        st[u] = fan_state(err, px[u]);
       }
       // probe lines (probe_line's addressing)
 #pragma unroll
@@ -4903,19 +4926,33 @@ __global__ __launch_bounds__(FAN_NT) __attribute__((amdgpu_waves_per_eu(5))) voi
           const v4u* lp = reinterpret_cast<const v4u*>((uintptr_t)pl[u]) + (uint64_t)(bucket >> (lgl - 1)) * 4;
 #pragma unroll
           for (int k = 0; k < 4; k++) Q[u][k] = lp[k];
+        } else {
+          // a defined value: an undefined one is carried from chunk to chunk in registers (ten
+          // VGPRs, and scratch in the instantiations that do not have them to spare)
+#pragma unroll
+          for (int k = 0; k < 4; k++) Q[u][k] = v4u{0u, 0u, 0u, 0u};
         }
       }
       // decode and store
 #pragma unroll
       for (int u = 0; u < FAN_U; u++) {
-        uint64_t r = 0;
+        uint64_t r = st[u] == 3 ? 1u : 0u;
         bool walk = st[u] == 2;
         if (st[u] == 1) walk = !line_decode(Q[u], pj[u], pr[u], px[u] & 0xff, (px[u] >> 16) & 0xff, r);
         if (walk) r = probe_group(groups[g[u]], hh[u]);
-        if (kk[u] < nk) __builtin_nontemporal_store(r, found + pbase + p0 + (uint64_t)u * WAVE);
+        if constexpr (EXISTS) {
+          const uint32_t bits = fan_exists_bits(st[u], r);
+          if (bits)  // a pair past the wave's keys names no member: no bits
+            (void)__hip_atomic_fetch_or(&s_ex[wv][kk[u] & (WAVE - 1)], bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        } else {
+          if (kk[u] < nk) __builtin_nontemporal_store(r, found + pbase + p0 + (uint64_t)u * WAVE);
+        }
       }
     }
     wave_sync_lds();  // the next chunk's keys, key window and hashes overwrite this one's
+    if constexpr (EXISTS) {  // after the sync: every lane's ORs are in; lane k clears s_ex[k] itself
+      if (lane < nk) found[wf + lane] = (uint8_t)s_ex[wv][lane];
+    }
   }
 }
 
@@ -4930,14 +4967,15 @@ __global__ __launch_bounds__(FAN_NT) __attribute__((amdgpu_waves_per_eu(5))) voi
 // step or chunk to the next. The entries of the keys past a partial wave's nk hold the wave's
 // pair count, so the search never names them. From the member id on the path is
 // k_probe_fanout's. A wave whose keys own no pairs reads its two end offsets and nothing else.
-template <int KIND>
+// EXISTS: a wave whose keys own no pairs still stores their bytes, all 0.
+template <int KIND, bool EXISTS>
 __global__ __launch_bounds__(FAN_NT) __attribute__((amdgpu_waves_per_eu(5))) void k_probe_fanout_ragged(const void* __restrict__ in0,
                                                                 const uint64_t* __restrict__ offs,
                                                                 uint32_t key_len, uint32_t seed,
                                                                 const ProbeGroup* __restrict__ groups, uint32_t ng,
                                                                 const uint32_t* __restrict__ member,
                                                                 const uint64_t* __restrict__ moff, uint64_t n,
-                                                                uint64_t* __restrict__ found) {
+                                                                fan_out_t<EXISTS>* __restrict__ found) {
   constexpr bool WAVE_KEYS = KIND == IN_KEYS24;
   constexpr bool WAVE_VAR = KIND == IN_VAR;
   constexpr int NW = FAN_NT / WAVE;
@@ -4945,6 +4983,7 @@ __global__ __launch_bounds__(FAN_NT) __attribute__((amdgpu_waves_per_eu(5))) voi
   __shared__ __attribute__((aligned(16))) uint32_t s_vk[WAVE_VAR ? NW : 1][WAVE_VAR ? FAN_VCAP / 4 + 4 : 1];
   __shared__ uint32_t s_h[NW][WAVE];
   __shared__ uint32_t s_off[NW][WAVE];  // off[k] - off[0] of the wave's keys; np past nk
+  __shared__ uint32_t s_ex[EXISTS ? NW : 1][EXISTS ? WAVE : 1];  // EXISTS: the bits of the wave's keys
   const uint32_t lane = threadIdx.x & (WAVE - 1);
   const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x) / WAVE;
   const uint64_t nwaves = (n + WAVE - 1) / WAVE;
@@ -4953,13 +4992,20 @@ __global__ __launch_bounds__(FAN_NT) __attribute__((amdgpu_waves_per_eu(5))) voi
     const uint32_t nk = (uint32_t)min<uint64_t>(WAVE, n - wf);
     const uint64_t pbase = moff[wf];                   // the wave's first pair
     const uint32_t np = (uint32_t)(moff[wf + nk] - pbase);  // its pairs (<= 64 * 65,535)
-    if (np == 0) continue;  // nothing of this chunk is in LDS: no sync owed
+    if (np == 0) {  // nothing of this chunk is in LDS: no sync owed
+      if constexpr (EXISTS) {
+        if (lane < nk) found[wf + lane] = 0;
+      }
+      continue;
+    }
     s_off[wv][lane] = lane < nk ? (uint32_t)(moff[wf + lane] - pbase) : np;
+    if constexpr (EXISTS) s_ex[wv][lane] = 0;
     const uint32_t h = fan_hash_chunk<KIND>(in0, offs, key_len, seed, wf, nk, lane, s_keys[wv], s_vk[wv]);
     s_h[wv][lane] = h;
     wave_sync_lds();
     for (uint32_t p0 = lane; p0 < np + lane; p0 += (uint32_t)WAVE * FAN_U) {  // p0 - lane: wave-uniform
       uint32_t g[FAN_U], st[FAN_U], px[FAN_U], pf[FAN_U], hh[FAN_U], pj[FAN_U], pr[FAN_U];
+      uint32_t ow[EXISTS ? FAN_U : 1];  // EXISTS: the pair's key, kept for its bits (and hh read again from it)
       v4u Q[FAN_U][4];
       // member ids: one coalesced read per step
 #pragma unroll
@@ -4972,7 +5018,9 @@ __global__ __launch_bounds__(FAN_NT) __attribute__((amdgpu_waves_per_eu(5))) voi
       // 64 whose hash nothing uses
 #pragma unroll
       for (int u = 0; u < FAN_U; u++) {
-        hh[u] = s_h[wv][wave_owner_of(s_off[wv], p0 + (uint32_t)u * WAVE)];
+        const uint32_t k = wave_owner_of(s_off[wv], p0 + (uint32_t)u * WAVE);
+        hh[u] = s_h[wv][k];
+        if constexpr (EXISTS) ow[u] = k;
       }
       // group heads: scalar loads through the constant address space when the whole wave names
       // one member, one plain load per lane otherwise
@@ -4999,8 +5047,7 @@ __global__ __launch_bounds__(FAN_NT) __attribute__((amdgpu_waves_per_eu(5))) voi
           pf[u] = G->fpl;
           pl[u] = (uint64_t)(uintptr_t)G->lines;
         }
-        // 0 nothing found, 1 probe line, 2 no lines or dense lines: probe_group
-        st[u] = err ? 0u : ((px[u] >> 24) - 1u < LINE_DENSE - 1u ? 1u : 2u);
+        st[u] = fan_state(err, px[u]);
       }
       // probe lines (probe_line's addressing)
 #pragma unroll
@@ -5015,20 +5062,38 @@ __global__ __launch_bounds__(FAN_NT) __attribute__((amdgpu_waves_per_eu(5))) voi
           const v4u* lp = reinterpret_cast<const v4u*>((uintptr_t)pl[u]) + (uint64_t)(bucket >> (lgl - 1)) * 4;
 #pragma unroll
           for (int k = 0; k < 4; k++) Q[u][k] = lp[k];
+        } else {
+          // a defined value: an undefined one is carried from chunk to chunk in registers (ten
+          // VGPRs, and scratch in the instantiations that do not have them to spare)
+#pragma unroll
+          for (int k = 0; k < 4; k++) Q[u][k] = v4u{0u, 0u, 0u, 0u};
         }
       }
       // decode and store
 #pragma unroll
       for (int u = 0; u < FAN_U; u++) {
         const uint32_t p = p0 + (uint32_t)u * WAVE;
-        uint64_t r = 0;
+        uint64_t r = st[u] == 3 ? 1u : 0u;
         bool walk = st[u] == 2;
         if (st[u] == 1) walk = !line_decode(Q[u], pj[u], pr[u], px[u] & 0xff, (px[u] >> 16) & 0xff, r);
-        if (walk) r = probe_group(groups[g[u]], hh[u]);
-        if (p < np) __builtin_nontemporal_store(r, found + pbase + p);
+        if constexpr (EXISTS) {
+          if (walk) r = probe_group(groups[g[u]], s_h[wv][ow[u]]);
+        } else {
+          if (walk) r = probe_group(groups[g[u]], hh[u]);
+        }
+        if constexpr (EXISTS) {
+          const uint32_t bits = fan_exists_bits(st[u], r);
+          if (bits)  // a pair past np names no member: no bits
+            (void)__hip_atomic_fetch_or(&s_ex[wv][ow[u]], bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        } else {
+          if (p < np) __builtin_nontemporal_store(r, found + pbase + p);
+        }
       }
     }
     wave_sync_lds();  // the next chunk's keys, key window, hashes and offsets overwrite this one's
+    if constexpr (EXISTS) {  // after the sync: every lane's ORs are in; lane k clears s_ex[k] itself
+      if (lane < nk) found[wf + lane] = (uint8_t)s_ex[wv][lane];
+    }
   }
 }
 
@@ -5126,10 +5191,11 @@ extern "C" void rf_fanout_set_max_blocks(uint32_t blocks) {
 
 // offs: the n + 1 byte offsets of IN_VAR keys (in0 = their bytes), unused by the other kinds.
 // moff == nullptr: the fixed form, K members per key; else the ragged form, moff = the n + 1 pair
-// offsets of the keys' member lists (K unused).
-extern "C" int rf_launch_probe_fanout(void* stream, int kind, const void* in0, const uint64_t* offs, uint32_t key_len,
-                                      uint32_t seed, const ProbeGroup* groups, uint32_t ng, const uint32_t* member,
-                                      uint32_t K, const uint64_t* moff, uint64_t n, uint64_t* found) {
+// offsets of the keys' member lists (K unused). EXISTS: out = the n bytes d_exists.
+template <bool EXISTS>
+static int launch_probe_fanout(void* stream, int kind, const void* in0, const uint64_t* offs, uint32_t key_len,
+                               uint32_t seed, const ProbeGroup* groups, uint32_t ng, const uint32_t* member,
+                               uint32_t K, const uint64_t* moff, uint64_t n, fan_out_t<EXISTS>* found) {
   if (n == 0) return 0;
   uint64_t nblk = ((n + WAVE - 1) / WAVE + FAN_NT / WAVE - 1) / (FAN_NT / WAVE);
   if (nblk > 0x7fffffffull) nblk = 0x7fffffffull;
@@ -5139,9 +5205,9 @@ extern "C" int rf_launch_probe_fanout(void* stream, int kind, const void* in0, c
   hipStream_t st = (hipStream_t)stream;
 #define L(KD)                                                                                                      \
   if (moff)                                                                                                        \
-    hipLaunchKernelGGL((k_probe_fanout_ragged<KD>), g, b, 0, st, in0, offs, key_len, seed, groups, ng, member, moff, n, found); \
+    hipLaunchKernelGGL((k_probe_fanout_ragged<KD, EXISTS>), g, b, 0, st, in0, offs, key_len, seed, groups, ng, member, moff, n, found); \
   else                                                                                                             \
-    hipLaunchKernelGGL((k_probe_fanout<KD>), g, b, 0, st, in0, offs, key_len, seed, groups, ng, member, K, n, found)
+    hipLaunchKernelGGL((k_probe_fanout<KD, EXISTS>), g, b, 0, st, in0, offs, key_len, seed, groups, ng, member, K, n, found)
   switch (kind) {
     KEY_KIND_CASES(L)
     case IN_HASH: L(IN_HASH); break;
@@ -5149,6 +5215,18 @@ extern "C" int rf_launch_probe_fanout(void* stream, int kind, const void* in0, c
   }
 #undef L
   return launch_status();
+}
+
+extern "C" int rf_launch_probe_fanout(void* stream, int kind, const void* in0, const uint64_t* offs, uint32_t key_len,
+                                      uint32_t seed, const ProbeGroup* groups, uint32_t ng, const uint32_t* member,
+                                      uint32_t K, const uint64_t* moff, uint64_t n, uint64_t* found) {
+  return launch_probe_fanout<false>(stream, kind, in0, offs, key_len, seed, groups, ng, member, K, moff, n, found);
+}
+extern "C" int rf_launch_probe_fanout_exists(void* stream, int kind, const void* in0, const uint64_t* offs,
+                                             uint32_t key_len, uint32_t seed, const ProbeGroup* groups, uint32_t ng,
+                                             const uint32_t* member, uint32_t K, const uint64_t* moff, uint64_t n,
+                                             uint8_t* exists) {
+  return launch_probe_fanout<true>(stream, kind, in0, offs, key_len, seed, groups, ng, member, K, moff, n, exists);
 }
 
 // ---- multi-get: member updates of a resident filter set ---------------------------------

@@ -68,6 +68,11 @@ int rf_launch_lookup_server(void* stream, const rf::SrvReq* ring, rf::SrvRes* re
 int rf_launch_probe_fanout(void* stream, int kind, const void* in0, const uint64_t* offs, uint32_t key_len,
                            uint32_t seed, const rf::ProbeGroup* groups, uint32_t ng, const uint32_t* member,
                            uint32_t K, const uint64_t* moff, uint64_t n, uint64_t* found);
+// the same walk as an existence lookup (the kernels' EXISTS instantiations): exists[i] = the OR of
+// RF_AMD_EXISTS_* over key i's pairs, every one of the n bytes written, no found word
+int rf_launch_probe_fanout_exists(void* stream, int kind, const void* in0, const uint64_t* offs, uint32_t key_len,
+                                  uint32_t seed, const rf::ProbeGroup* groups, uint32_t ng, const uint32_t* member,
+                                  uint32_t K, const uint64_t* moff, uint64_t n, uint8_t* exists);
 // k_set_update: a->n <= SET_UPD_PER_LAUNCH entries into the table a->groups, one launch
 int rf_launch_set_update(void* stream, const rf::SetUpdate* a);
 // diagnostics (rf_amd_diag_fanout_max_blocks): a cap on both fan-out grids; 0 = none

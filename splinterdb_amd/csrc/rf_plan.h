@@ -180,6 +180,12 @@ struct ProbeGroup {
   const uint8_t* pages;   // the filter's data pages
   const uint64_t* slots;  // the filter's (relocatable) index slots
 };
+// Tables of filter sets only (rf_amd_filter_set): the NULL entry -- err != 0, nothing
+// dereferenced -- with this bit of `err` is a bundle without a maplet that holds one branch
+// (RF_AMD_MEMBER_UNFILTERED, src/trunk.c:6020-6022): every key's found word is 1. The build's
+// error bits are ERR_* (1, 2, 4, 8); k_probe_groups, k_probe_small and the lookup server never
+// meet the bit, no set's entry reaching them.
+constexpr uint32_t GROUP_UNFILTERED = 0x80000000u;
 
 // The lookup server (k_lookup_server): single lookups travel through a ring of requests that a
 // persistent wave polls, instead of one kernel launch per call. The ring lives in fine-grained
@@ -237,7 +243,7 @@ struct SmallProbe {
 // entry is the member's host-resolved table entry -- g.err holding the error bits the host
 // already knows (0: none) -- the slot it goes to, and where the member's build leaves its error
 // bits, read on the device in stream order (nullptr: a NULL member, which is the all-zero
-// entry with err = 1)
+// entry with err = 1, or an unfiltered one, the same with GROUP_UNFILTERED: stored as it stands)
 constexpr uint32_t SET_UPD_PER_LAUNCH = 64;
 struct SetUpdEntry {
   ProbeGroup g;

@@ -16,15 +16,21 @@
 
 namespace rf {
 
+// what an entry puts into a slot: a filter, NULL_ROUTING_FILTER (a bundle with no branch), or
+// RF_AMD_MEMBER_UNFILTERED (a bundle without a maplet that holds one branch)
+enum SetMemberKind : uint8_t { SET_FILTER = 0, SET_NULL = 1, SET_UNFILTERED = 2 };
+
 // what the host keeps of a set: its size, the members' count (one past the largest id ever
-// set), each slot's seed and whether a filter sits in it, and the seed rule these give -- `seed`
-// is the seed of the first occupied slot (0: none), one_seed whether every occupied slot has it
+// set), each slot's seed, whether a filter sits in it and its kind, and the seed rule these give
+// -- `seed` is the seed of the first occupied slot (0: none), one_seed whether every occupied
+// slot has it. Only a filter occupies a slot: an unfiltered member hashes nothing.
 struct SetState {
   uint32_t capacity = 0, num_members = 0;
   uint32_t seed = 0;
   bool one_seed = true;
   std::vector<uint32_t> slot_seed;  // capacity
   std::vector<uint8_t> occupied;    // capacity
+  std::vector<uint8_t> kind;        // capacity: SetMemberKind (a slot never set: SET_NULL)
   // scratch of the deduplication: mark[id] == gen, entry of id seen in this call
   std::vector<uint32_t> mark;
   uint32_t gen = 0;
@@ -33,6 +39,7 @@ struct SetState {
     capacity = cap;
     slot_seed.assign(cap, 0u);
     occupied.assign(cap, 0);
+    kind.assign(cap, SET_NULL);
     mark.assign(cap, 0u);
   }
 };
@@ -46,9 +53,10 @@ struct SetUpdatePlan {
   uint32_t launches() const { return cuts.empty() ? 0u : (uint32_t)cuts.size() - 1; }
 };
 
-// the call: entry i sets member ids[i] to a filter hashed with seeds[i], or, is_null[i], to
-// NULL_ROUTING_FILTER (seeds[i] is not read then; is_null == nullptr: none is)
-inline int plan_set_update(SetState* s, uint32_t count, const uint32_t* ids, const uint8_t* is_null,
+// the call: entry i sets member ids[i] to what kind[i] names (SetMemberKind; kind == nullptr:
+// every entry is a filter): a filter hashed with seeds[i], NULL_ROUTING_FILTER or an unfiltered
+// member (seeds[i] is not read for these two); any other value is refused
+inline int plan_set_update(SetState* s, uint32_t count, const uint32_t* ids, const uint8_t* kind,
                            const uint32_t* seeds, SetUpdatePlan* plan, std::string* err) {
   auto refuse = [&](const char* m) {
     if (err) *err = m;
@@ -58,6 +66,8 @@ inline int plan_set_update(SetState* s, uint32_t count, const uint32_t* ids, con
   if (count && (!ids || !seeds)) return refuse("null member arrays");
   for (uint32_t i = 0; i < count; i++)
     if (ids[i] >= s->capacity) return refuse("member id >= capacity");
+  for (uint32_t i = 0; kind && i < count; i++)
+    if (kind[i] > SET_UNFILTERED) return refuse("unknown member kind");
   // nothing above has written anything; nothing below fails
   if (++s->gen == 0) {  // the counter wrapped: stale marks could match again
     s->mark.assign(s->capacity, 0u);
@@ -72,9 +82,10 @@ inline int plan_set_update(SetState* s, uint32_t count, const uint32_t* ids, con
     if (s->mark[id] == s->gen) continue;
     s->mark[id] = s->gen;
     plan->order[count - ++kept] = i;
-    const bool null = is_null && is_null[i];
-    s->occupied[id] = null ? 0 : 1;
-    s->slot_seed[id] = null ? 0u : seeds[i];
+    const uint8_t k = kind ? kind[i] : (uint8_t)SET_FILTER;
+    s->kind[id] = k;
+    s->occupied[id] = k == SET_FILTER ? 1 : 0;
+    s->slot_seed[id] = k == SET_FILTER ? seeds[i] : 0u;
     if (id + 1 > top) top = id + 1;
   }
   plan->order.erase(plan->order.begin(), plan->order.begin() + (count - kept));

@@ -75,6 +75,9 @@ EXPORTED = [
     "rf_amd_diag_range_seg_launch_ids", "rf_amd_diag_range_seg_thread_ids",
     "rf_amd_found_per_key_scratch_bytes", "rf_amd_found_per_key", "rf_amd_found_per_key_ragged",
     "rf_amd_diag_per_key_tile",
+    "rf_amd_filter_set_exists_keys", "rf_amd_filter_set_exists_var_keys", "rf_amd_filter_set_exists_hashes",
+    "rf_amd_filter_set_exists_keys_ragged", "rf_amd_filter_set_exists_var_keys_ragged",
+    "rf_amd_filter_set_exists_hashes_ragged",
 ]
 ROUTE_MAX_WORLD = 16
 FOUND_COMPACT_TILE = 4096  # found words per workgroup of rf_amd_found_compact (FC_TILE)
@@ -271,6 +274,12 @@ def load_library(build_if_missing=True):
     L.rf_amd_filter_set_probe_keys_ragged.argtypes = [vp, vp, u32, vp, vp, u64, vp, vp]
     L.rf_amd_filter_set_probe_var_keys_ragged.argtypes = [vp, vp, vp, vp, vp, u64, vp, vp]
     L.rf_amd_filter_set_probe_hashes_ragged.argtypes = [vp, vp, vp, vp, u64, vp, vp]
+    L.rf_amd_filter_set_exists_keys.argtypes = L.rf_amd_filter_set_probe_keys.argtypes
+    L.rf_amd_filter_set_exists_hashes.argtypes = L.rf_amd_filter_set_probe_hashes.argtypes
+    L.rf_amd_filter_set_exists_var_keys.argtypes = L.rf_amd_filter_set_probe_var_keys.argtypes
+    L.rf_amd_filter_set_exists_keys_ragged.argtypes = L.rf_amd_filter_set_probe_keys_ragged.argtypes
+    L.rf_amd_filter_set_exists_var_keys_ragged.argtypes = L.rf_amd_filter_set_probe_var_keys_ragged.argtypes
+    L.rf_amd_filter_set_exists_hashes_ragged.argtypes = L.rf_amd_filter_set_probe_hashes_ragged.argtypes
     L.rf_amd_diag_fanout_max_blocks.argtypes = [u32]
     L.rf_amd_range_map_create.argtypes = [vp, u32, vp, vp, vp, vp, ctypes.POINTER(vp)]
     L.rf_amd_range_map_destroy.argtypes = [vp]
@@ -1080,6 +1089,56 @@ def found_per_key_ragged(d_found, d_member, d_member_off, n, d_key_off, d_cand, 
                    n, d_key_off, d_cand, d_cand_key, d_count, stream, engine)
 
 
+_exists_routed_csr = {}  # (engine, stream) -> the CSR of the last exists_routed issued there
+
+
+class _Unfiltered:
+    """RF_AMD_MEMBER_UNFILTERED: a bundle without a maplet that holds one branch
+    (src/trunk.c:6020-6022); every key finds value 0 in it"""
+
+    def __repr__(self):
+        return "UNFILTERED"
+
+
+UNFILTERED = _Unfiltered()
+EXISTS_FILTER_HIT = 1  # RF_AMD_EXISTS_FILTER_HIT: some filter of the key's list found a value
+EXISTS_UNFILTERED = 2  # RF_AMD_EXISTS_UNFILTERED: the list holds an unfiltered member
+KIND_FILTER, KIND_NULL, KIND_UNFILTERED = 0, 1, 2  # what a set's slot holds (exists_host's kinds)
+
+
+def exists_host(words, kinds, member, member_off):
+    """Host mirror of rf_amd_filter_set_exists_*_ragged: words[p] = the oracle's found word of
+    pair p where its member is a filter (not read elsewhere), kinds[g] = KIND_* of member g of
+    the set, member and member_off the call's, all indexed by the absolute pair (member_off[0]
+    any value). An id >= len(kinds) adds nothing, as a NULL member. Returns the n bytes: bit 0
+    when a filter of the key's list has a non-zero word, bit 1 when the list holds an unfiltered
+    member."""
+    off = np.ascontiguousarray(member_off).reshape(-1).view(np.uint64).astype(np.int64)
+    first, last, n = int(off[0]), int(off[-1]), off.size - 1
+    ids = np.ascontiguousarray(member).reshape(-1).view(np.uint32)[first:last].astype(np.int64)
+    kinds = np.asarray(kinds, dtype=np.int64).reshape(-1)
+    ok = ids < kinds.size
+    kind = np.where(ok, kinds[np.where(ok, ids, 0)] if kinds.size else KIND_NULL, KIND_NULL)
+    w = np.ascontiguousarray(words).reshape(-1).view(np.uint64)[first:last]
+    bits = np.where((kind == KIND_FILTER) & (w != 0), EXISTS_FILTER_HIT, 0) | \
+        np.where(kind == KIND_UNFILTERED, EXISTS_UNFILTERED, 0)
+    key = np.repeat(np.arange(n), np.diff(off))
+    out = np.zeros(n, dtype=np.uint8)
+    for b in (EXISTS_FILTER_HIT, EXISTS_UNFILTERED):
+        out[np.unique(key[(bits & b) != 0])] |= np.uint8(b)
+    return out
+
+
+def exists_host_fixed(words, kinds, member, K):
+    """Host mirror of rf_amd_filter_set_exists_{keys,var_keys,hashes}: the pair of (key i, slot
+    j) is i * K + j; member None: the id is the slot. Returns what exists_host does."""
+    w = np.ascontiguousarray(words).reshape(-1).view(np.uint64)
+    n = w.size // K
+    if member is None:
+        member = np.tile(np.arange(K, dtype=np.uint32), n)
+    return exists_host(w, kinds, member, np.arange(n + 1, dtype=np.uint64) * np.uint64(K))
+
+
 def diag_fanout_max_blocks(blocks: int):
     """rf_amd_diag_fanout_max_blocks: cap the fan-out probe's grid (diagnostics, process-wide)
     so that every wave takes several 64-key chunks; 0 restores the default"""
@@ -1088,8 +1147,10 @@ def diag_fanout_max_blocks(blocks: int):
 
 class FilterSet:
     """A resident table of filters of any batches (rf_amd_filter_set): members = [(FilterBatch,
-    index) or None]. The member batches must outlive the set's last probe. capacity (None: the
-    number of members) is the room update() has: the slots past the members start empty."""
+    index), None (a bundle with no branch) or UNFILTERED (a bundle without a maplet that holds one
+    branch: every key's word is 1)]. The member batches must outlive the set's last probe.
+    capacity (None: the number of members) is the room update() has: the slots past the members
+    start empty."""
 
     def __init__(self, members, engine=None, capacity=None):
         self.engine = engine or default_engine()
@@ -1104,8 +1165,12 @@ class FilterSet:
                                                                n, int(capacity), ctypes.byref(h)))
         self.h = h
         self.num_members = n
-        self._members = list(members) + [None] * (self.capacity - n)  # slot -> (batch, index) or None
-        self._keep = [m[0] for m in self._members if m is not None]
+        self._members = list(members) + [None] * (self.capacity - n)  # slot -> (batch, index), None or UNFILTERED
+        self._keep = self._batches(self._members)
+
+    @staticmethod
+    def _batches(members):
+        return [m[0] for m in members if m is not None and m is not UNFILTERED]
 
     @staticmethod
     def _member_arrays(members):
@@ -1113,7 +1178,9 @@ class FilterSet:
         hs = (ctypes.c_void_p * max(1, n))()
         idx = np.zeros(max(1, n), dtype=np.uint32)
         for i, m in enumerate(members):
-            if m is not None:
+            if m is UNFILTERED:
+                hs[i] = 1  # RF_AMD_MEMBER_UNFILTERED
+            elif m is not None:
                 hs[i] = m[0].h.value
                 idx[i] = m[1]
         return hs, idx
@@ -1123,8 +1190,8 @@ class FilterSet:
         return load_library().rf_amd_filter_set_capacity(self.h)
 
     def update(self, ids, members, stream=None):
-        """rf_amd_filter_set_update: slot ids[i] becomes members[i] -- (FilterBatch, index), or
-        None to clear it -- in stream order, without a host wait (the caller orders the members'
+        """rf_amd_filter_set_update: slot ids[i] becomes members[i] -- (FilterBatch, index),
+        UNFILTERED, or None to clear it -- in stream order, without a host wait (the caller orders the members'
         builds before the call, on the same stream or with an event). An id named twice: the
         last entry wins. num_members follows the call. Returns what slot ids[i] held before the
         call, entry by entry; the set references the new batches afterwards and the replaced ones
@@ -1143,7 +1210,7 @@ class FilterSet:
         replaced = [self._members[int(i)] for i in ids]
         for i, m in zip(ids, members):
             self._members[int(i)] = m
-        self._keep = [m[0] for m in self._members if m is not None]
+        self._keep = self._batches(self._members)
         self.num_members = L.rf_amd_filter_set_num_members(self.h)
         return replaced
 
@@ -1217,6 +1284,59 @@ class FilterSet:
         _check(load_library().rf_amd_filter_set_probe_hashes_ragged(self.h, _dptr(d_hashes), _dptr(d_member),
                                                                     _dptr(d_member_off), n, _dptr(d_found),
                                                                     _stream(stream)))
+
+    # ---- existence multi-get (rf_amd_filter_set_exists_*): the probes' arguments with d_exists, n
+    # bytes (uint8, any alignment), in d_found's place; d_exists[i] = EXISTS_FILTER_HIT when a filter
+    # of key i's list found a value | EXISTS_UNFILTERED when the list holds an unfiltered member
+    def exists_keys(self, d_keys, key_len, d_member, K, n, d_exists, stream=None):
+        _check(load_library().rf_amd_filter_set_exists_keys(self.h, _dptr(d_keys), key_len, _dptr(d_member), K, n,
+                                                            _dptr(d_exists), _stream(stream)))
+
+    def exists_hashes(self, d_hashes, d_member, K, n, d_exists, stream=None):
+        _check(load_library().rf_amd_filter_set_exists_hashes(self.h, _dptr(d_hashes), _dptr(d_member), K, n,
+                                                              _dptr(d_exists), _stream(stream)))
+
+    def exists_var_keys(self, d_bytes, d_offsets, d_member, K, n, d_exists, stream=None):
+        _check(load_library().rf_amd_filter_set_exists_var_keys(self.h, _dptr(d_bytes), _dptr(d_offsets),
+                                                                _dptr(d_member), K, n, _dptr(d_exists),
+                                                                _stream(stream)))
+
+    def exists_keys_ragged(self, d_keys, key_len, d_member, d_member_off, n, d_exists, stream=None):
+        _check(load_library().rf_amd_filter_set_exists_keys_ragged(self.h, _dptr(d_keys), key_len, _dptr(d_member),
+                                                                   _dptr(d_member_off), n, _dptr(d_exists),
+                                                                   _stream(stream)))
+
+    def exists_var_keys_ragged(self, d_bytes, d_offsets, d_member, d_member_off, n, d_exists, stream=None):
+        _check(load_library().rf_amd_filter_set_exists_var_keys_ragged(self.h, _dptr(d_bytes), _dptr(d_offsets),
+                                                                       _dptr(d_member), _dptr(d_member_off), n,
+                                                                       _dptr(d_exists), _stream(stream)))
+
+    def exists_hashes_ragged(self, d_hashes, d_member, d_member_off, n, d_exists, stream=None):
+        _check(load_library().rf_amd_filter_set_exists_hashes_ragged(self.h, _dptr(d_hashes), _dptr(d_member),
+                                                                     _dptr(d_member_off), n, _dptr(d_exists),
+                                                                     _stream(stream)))
+
+    def exists_routed(self, range_map, d_keys, key_len, n, stream=None):
+        """RangeMap.route_keys + exists_keys_ragged, from raw device keys: the n bytes (a uint8
+        tensor). No host read: the route call's CSR goes to the existence call as it is."""
+        return self._exists_routed(n, stream, range_map.route_keys(d_keys, key_len, n, stream=stream),
+                                   lambda *a: self.exists_keys_ragged(d_keys, key_len, *a))
+
+    def exists_var_routed(self, range_map, d_bytes, d_offsets, n, stream=None):
+        """exists_routed for variable-length keys (route_var_keys + exists_var_keys_ragged)"""
+        return self._exists_routed(n, stream, range_map.route_var_keys(d_bytes, d_offsets, n, stream=stream),
+                                   lambda *a: self.exists_var_keys_ragged(d_bytes, d_offsets, *a))
+
+    def _exists_routed(self, n, stream, routed, exists):
+        import torch
+        _, d_off, d_member, _ = routed
+        if d_member.numel() == 0:  # a map whose lists are all empty
+            return torch.zeros(n, dtype=torch.uint8, device=d_off.device)
+        d_exists = torch.empty(n, dtype=torch.uint8, device=d_off.device)
+        exists(d_member, d_off, n, d_exists, stream)
+        # the CSR is read in stream order: kept until the next call on the same stream
+        _exists_routed_csr[(id(self.engine), _stream(stream))] = (d_off, d_member)
+        return d_exists
 
     def multiget_ragged(self, d_keys, key_len, d_member, d_member_off, n, cap=None, stream=None):
         """probe_keys_ragged + found_compact over the pairs: returns (d_cand, count, d_key). The

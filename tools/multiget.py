@@ -73,7 +73,16 @@ minimum, maximum and median, the parent path's round-to-round spread, and whethe
 median is within that spread of the parent path's. Default output: profiles/multiget_per_key.json
 (profiles/multiget_var_per_key.json).
 
-    timeout -k 10 600 python tools/multiget.py [--var] [--ragged | --routed | --per-key] [--filters 64] [--keys 1048576]
+--exists: the existence multi-get (SPLINTERDB_LOOKUP_MIGHT_EXIST), on the same two workloads (with
+--var: variable-length keys). (exists) one rf_amd_filter_set_exists_*_ragged: one byte per key.
+(ragged_probe) the parent path's cheapest possible start: the ragged probe alone on the same
+inputs, which writes 8 bytes per pair that a second pass would still have to reduce -- a lower bound
+of any way to get the answer from the calls there were. Every byte is compared with "some word of
+the key's pairs is not zero" before anything is timed; then alternating rounds with the same
+method and the same condition as --per-key. Default output: profiles/multiget_exists.json
+(profiles/multiget_var_exists.json).
+
+    timeout -k 10 600 python tools/multiget.py [--var] [--ragged | --routed | --per-key | --exists] [--filters 64] [--keys 1048576]
                                                [--n 16777216] [--k 4] [--rounds 7] [--warmup 2]
                                                [--out profiles/multiget.json]
     timeout -k 10 300 python tools/multiget.py --update --filters 1024 --keys 4096
@@ -386,17 +395,14 @@ def routed(args, fset, eng, stream, kin, timed, rng):
     return out
 
 
-def per_key(args, fset, eng, stream, kin, timed, rng):
-    """--per-key: candidates with member ids, keys and a CSR over the keys, two ways, on the
-    --ragged lists and on the CSR of a route call; kin: the keys' arguments"""
-    import statistics
-
+def csr_workloads(args, eng, stream, kin, hr):
+    """the two member-list workloads of --per-key and --exists as (name, make) pairs, make()
+    returning (d_member_off, d_member, pairs): the --ragged lists and the CSR of a route call
+    through a map of ROUTED_R such lists; hr: the host generator both draw from, in this order"""
     import numpy as np
     F, n, R = args.filters, args.n, ROUTED_R
     st = stream.cuda_stream
     dev = kin[0].device
-    hr = np.random.default_rng(13)
-    probe_r = fset.probe_var_keys_ragged if args.var else fset.probe_keys_ragged
 
     def geometric(size):
         return np.minimum(KPAD, 1 + hr.geometric(1.0 / 3.0, size=size)).astype(np.int64)
@@ -439,6 +445,21 @@ def per_key(args, fset, eng, stream, kin, timed, rng):
         del d_off, d_member
         rmap.close()
         return off, member, m
+
+    return (("ragged", ragged_csr), ("routed", routed_csr))
+
+
+def per_key(args, fset, eng, stream, kin, timed, rng):
+    """--per-key: candidates with member ids, keys and a CSR over the keys, two ways, on the
+    --ragged lists and on the CSR of a route call; kin: the keys' arguments"""
+    import statistics
+
+    import numpy as np
+    F, n, R = args.filters, args.n, ROUTED_R
+    st = stream.cuda_stream
+    dev = kin[0].device
+    hr = np.random.default_rng(13)
+    probe_r = fset.probe_var_keys_ragged if args.var else fset.probe_keys_ragged
 
     def measure(off, member, m):
         with torch.cuda.stream(stream):
@@ -519,13 +540,90 @@ def per_key(args, fset, eng, stream, kin, timed, rng):
         "config": {"filters": F, "keys_per_filter": args.keys, "n": n, "ranges": R, "rounds": args.rounds,
                    "warmup": args.warmup, "fingerprint_size": 26, "log_index_size": 8},
     }
-    for name, csr in (("ragged", ragged_csr), ("routed", routed_csr)):
+    for name, csr in csr_workloads(args, eng, stream, kin, hr):
         off, member, m = csr()
         out[name] = measure(off, member, m)
         del off, member
     out["verified"] = ("before timing, on both workloads: totals equal; every record equal to member[pair] << 8 | value "
                        "of found_compact's record; every record's key equal to searchsorted's; the offsets equal "
                        "to the starts of the keys' runs")
+    out["device"] = torch.cuda.get_device_name(0)
+    return out
+
+
+def exists(args, fset, eng, stream, kin, timed, rng):
+    """--exists: the existence multi-get against the ragged probe alone, on the --ragged lists and
+    on the CSR of a route call; kin: the keys' arguments"""
+    import statistics
+
+    import numpy as np
+    F, n, R = args.filters, args.n, ROUTED_R
+    st = stream.cuda_stream
+    dev = kin[0].device
+    hr = np.random.default_rng(13)
+    probe_r = fset.probe_var_keys_ragged if args.var else fset.probe_keys_ragged
+    exists_r = fset.exists_var_keys_ragged if args.var else fset.exists_keys_ragged
+
+    def measure(off, member, m):
+        with torch.cuda.stream(stream):
+            found = torch.zeros(m, dtype=torch.int64, device=dev)
+            d_exists = torch.full((n,), 0xAB, dtype=torch.uint8, device=dev)
+            # both once, compared before anything is timed: the set holds filters only, so the byte
+            # is "some word of the key's pairs is not zero"
+            probe_r(*kin, member, off, n, found, stream=st)
+            exists_r(*kin, member, off, n, d_exists, stream=st)
+        stream.synchronize()
+        with torch.cuda.stream(stream):
+            key = torch.repeat_interleave(torch.arange(n, device=dev), off[1:] - off[:-1])
+            want = torch.zeros(n, dtype=torch.uint8, device=dev)
+            want[key[found != 0]] = E.EXISTS_FILTER_HIT
+            assert torch.equal(d_exists, want), "the bytes differ from the ragged probe's words"
+            hits = int(want.sum())
+            del key, want
+        stream.synchronize()
+        ways = {"ragged_probe": lambda: probe_r(*kin, member, off, n, found, stream=st),
+                "exists": lambda: exists_r(*kin, member, off, n, d_exists, stream=st)}
+        t = {w: [] for w in ways}
+        for r in range(args.warmup + args.rounds):
+            for w, fn in ways.items():  # alternating: one of each per round
+                ms = timed(fn)
+                if r >= args.warmup:
+                    t[w].append(ms)
+        a, b = t["ragged_probe"], t["exists"]
+        spread = max(a) - min(a)
+        return {
+            "pairs": m, "mean_list": round(m / n, 4), "keys_that_might_exist": hits,
+            "ms": {w: dict(rng(v), median=round(statistics.median(v), 4)) for w, v in t.items()},
+            "parent_spread_ms": round(spread, 4),
+            # the condition: the existence call's median is not above the ragged probe's by more than
+            # that probe's own round-to-round spread
+            "exists_within_parent_spread": bool(statistics.median(b) <= statistics.median(a) + spread),
+            "ranges_touch": not (max(a) < min(b) or max(b) < min(a)),
+            "exists_faster_beyond_ranges": bool(max(b) < min(a)),
+            "exists_slower_beyond_ranges": bool(max(a) < min(b)),
+            "ragged_probe_output_bytes": 8 * m,
+            "exists_output_bytes": n,
+        }
+
+    out = {
+        "what": ("existence multi-get of n %s (rf_amd_filter_set_exists_%skeys_ragged: one byte per key, no found "
+                 "word) against the cheapest possible start of any way to get the answer from the parent commit, the "
+                 "ragged probe alone on the same inputs (8 bytes per pair, still to be reduced); on the --ragged lists "
+                 "(min(16, 1 + Geometric(1/3)) random members of one batch of F filters per key) and on the CSR of a "
+                 "route call through a map of R such lists; alternating rounds in one process, HIP events on the "
+                 "launch stream" % (("variable-length keys (keys.var_keys, 8-100 B)", "var_") if args.var
+                                    else ("24-byte keys", ""))),
+        "config": {"filters": F, "keys_per_filter": args.keys, "n": n, "ranges": R, "rounds": args.rounds,
+                   "warmup": args.warmup, "fingerprint_size": 26, "log_index_size": 8},
+    }
+    for name, csr in csr_workloads(args, eng, stream, kin, hr):
+        off, member, m = csr()
+        out[name] = measure(off, member, m)
+        del off, member
+    out["exists_within_parent_spread"] = bool(out["ragged"]["exists_within_parent_spread"] and
+                                              out["routed"]["exists_within_parent_spread"])
+    out["verified"] = ("before timing, on both workloads: every key's byte equal to 'some found word of the key's "
+                       "pairs, from the ragged probe of the same inputs, is not zero'")
     out["device"] = torch.cuda.get_device_name(0)
     return out
 
@@ -863,6 +961,8 @@ def main():
                     help="route + ragged probe + compaction from raw keys through a range map")
     ap.add_argument("--per-key", dest="per_key", action="store_true",
                     help="rf_amd_found_per_key_ragged against found_compact + searchsorted + gather")
+    ap.add_argument("--exists", action="store_true",
+                    help="rf_amd_filter_set_exists_*_ragged against the ragged probe alone")
     ap.add_argument("--update", action="store_true",
                     help="member updates of a resident set against destroy + create of the whole set")
     ap.add_argument("--segments", action="store_true",
@@ -871,7 +971,8 @@ def main():
     args = ap.parse_args()
     if args.out is None:
         name = "multiget" + ("_var" if args.var else "") + ("_ragged" if args.ragged else "") + \
-            ("_routed" if args.routed else "") + ("_per_key" if args.per_key else "") + ".json"
+            ("_routed" if args.routed else "") + ("_per_key" if args.per_key else "") + \
+            ("_exists" if args.exists else "") + ".json"
         name = "multiget_update.json" if args.update else "range_segments.json" if args.segments else name
         args.out = os.path.join(ROOT, "profiles", name)
     if not torch.cuda.is_available():
@@ -953,10 +1054,12 @@ def main():
     def rng(v):
         return {"min": round(min(v), 4), "max": round(max(v), 4), "rounds": [round(x, 4) for x in v]}
 
-    if args.ragged or args.routed or args.per_key:
+    if args.ragged or args.routed or args.per_key or args.exists:
         del found_a, found_b, member
         kin = (d_bytes, d_offs) if args.var else (keys, 24)
-        if args.per_key:
+        if args.exists:
+            out = exists(args, fset, eng, stream, kin, timed, rng)
+        elif args.per_key:
             out = per_key(args, fset, eng, stream, kin, timed, rng)
         elif args.routed:
             out = routed(args, fset, eng, stream, kin, timed, rng)
