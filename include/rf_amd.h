@@ -397,6 +397,46 @@ int rf_amd_found_per_key_ragged(rf_amd_engine *e, const uint64_t *d_found, const
                                 const uint64_t *d_member_off, uint64_t n, uint64_t *d_key_off,
                                 uint64_t *d_cand, uint64_t *d_cand_key, uint64_t cap, uint64_t *d_count,
                                 void *d_scratch, void *stream);
+/* group by branch: the step between rf_amd_found_per_key* and a consumer that looks a whole batch
+ * up together. Every record member_id << 8 | value names one B-tree,
+ * bundle_of[member]->branches[value]; the records come key by key (the order of the loop of
+ * trunk_ondisk_bundle_merge_lookup, src/trunk.c:6057-6087), and this call groups them by branch,
+ * stably, so that all keys that go into one tree stand side by side and in batch order, with a
+ * table of the branches that occur.
+ * d_cand, d_count and cap are what a rf_amd_found_per_key* call wrote and was given; the call
+ * works on the first m = min(*d_count, cap) records. *d_count is read on the device: the host
+ * never waits for it, and every size it needs comes from cap. The sort key of a record c is
+ * ((c >> 8) & (2^mb - 1)) << 6 | (c & 63), mb being the bit width of num_members - 1 (0 for one
+ * member): for ids below num_members that is (member, value) ascending. Ids at or above
+ * num_members are the caller's error; they are masked, not validated, so the call stays in bounds
+ * and the result is still defined.
+ * d_order[t], t < m, is the position j in d_cand of the record at grouped position t: a
+ * permutation of [0, m), ascending in the sort key and stable, so within one branch the records
+ * keep their input order, the batch's key order. d_order_key[t] = d_cand_key[d_order[t]] is
+ * optional: both pointers non-NULL, or both NULL and it is not produced. d_branch[u] is the full
+ * 64-bit record of the first element of branch run u, d_branch_off[u] the start of that run in
+ * d_order, and the entry behind the last written branch is m: d_branch_off holds branch_cap + 1
+ * words (with branch_cap == 0 it may be NULL and is then not written). *d_num_branches is the
+ * true number of runs, also when it exceeds branch_cap. Nothing is written at or past
+ * d_branch[branch_cap), d_branch_off[branch_cap + 1) or d_order[cap). With m == 0 the call writes
+ * *d_num_branches = 0 and d_branch_off[0] = 0 and nothing else.
+ * Asynchronous on stream (NULL = the engine's), no allocation, no synchronisation, no atomics on
+ * global memory, no workgroup waits for another; the same input gives the same bytes. The
+ * launches are known from num_members alone: a least-significant-digit radix sort in digits of 8
+ * bits, four launches per pass -- the histogram, the two levels of its scan and the scatter -- (1 pass up to 4 members, 2 up to 1,024, 3 up to 2^18, else 4) and
+ * three for the run table. d_scratch (8-byte aligned) holds
+ * rf_amd_found_by_branch_scratch_bytes(cap, num_members) bytes (callable without a device;
+ * non-decreasing in cap; a multiple of 8; never 0).
+ * EINVAL: a NULL engine; a NULL d_count or d_num_branches; num_members == 0 or > 2^26 (the sort
+ * key fits 32 bits); cap >= 2^32; a NULL d_cand, d_order or d_scratch with cap > 0; a NULL
+ * d_branch or d_branch_off with branch_cap > 0; a scratch that is not 8-byte aligned; exactly one
+ * of d_cand_key and d_order_key NULL. */
+uint64_t rf_amd_found_by_branch_scratch_bytes(uint64_t cap, uint32_t num_members);
+int rf_amd_found_by_branch(rf_amd_engine *e, const uint64_t *d_cand, const uint64_t *d_cand_key,
+                           const uint64_t *d_count, uint64_t cap, uint32_t num_members,
+                           uint32_t *d_order, uint64_t *d_order_key,
+                           uint64_t *d_branch, uint64_t *d_branch_off, uint64_t branch_cap,
+                           uint64_t *d_num_branches, void *d_scratch, void *stream);
 /* ---- range maps: multi-get keys routed to their member lists on the device ----------------
  * What produces the ragged probe's per-key lists. At each node on its trunk path a key takes
  * the last pivot whose key is <= it (trunk_ondisk_node_find_pivot, src/trunk.c:5886-5932,

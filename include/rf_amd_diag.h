@@ -119,6 +119,12 @@ uint32_t rf_amd_diag_range_seg_thread_ids(void);
 /* the keys of one tile of rf_amd_found_per_key / _ragged (the unit of their scratch and of their
  * grid-stride loops, which honour rf_amd_diag_fanout_max_blocks like the route kernels) */
 uint32_t rf_amd_diag_per_key_tile(void);
+/* the records of one tile of rf_amd_found_by_branch (the unit of its scratch and of its
+ * grid-stride loops, which honour rf_amd_diag_fanout_max_blocks too), and the digit passes of its
+ * sort for num_members (0 for a num_members the call refuses): a test takes one num_members on
+ * each side of every value at which the count changes */
+uint32_t rf_amd_diag_by_branch_tile(void);
+uint32_t rf_amd_diag_by_branch_passes(uint32_t num_members);
 
 /* the source id the library was built from (16 hex digits of SHA-256 over the engine's
  * sources and headers, splinterdb_amd/build.py source_id): the Python loader refuses a

@@ -2322,6 +2322,7 @@ extern "C" int rf_amd_diag_fanout_max_blocks(uint32_t blocks) {
   rf_fanout_set_max_blocks(blocks);
   rf_range_set_max_blocks(blocks);
   rf_per_key_set_max_blocks(blocks);
+  rf_by_branch_set_max_blocks(blocks);
   return 0;
 }
 
@@ -2374,6 +2375,31 @@ extern "C" int rf_amd_found_per_key_ragged(rf_amd_engine* e, const uint64_t* d_f
                                            void* d_scratch, void* stream) {
   return found_per_key(e, true, d_found, d_member, d_member_off, 0, n, d_key_off, d_cand, d_cand_key, cap, d_count,
                        d_scratch, stream);
+}
+
+// ---- group by branch: the per-key records in the order a batch's consumer walks the B-trees ---
+// The sizing and the argument checks are rf_by_branch_plan.h's, the kernels rf_by_branch.hip's.
+extern "C" uint64_t rf_amd_found_by_branch_scratch_bytes(uint64_t cap, uint32_t num_members) {
+  return by_branch_scratch_bytes(cap, num_members);
+}
+extern "C" uint32_t rf_amd_diag_by_branch_tile(void) { return BY_BRANCH_TILE; }
+extern "C" uint32_t rf_amd_diag_by_branch_passes(uint32_t num_members) {
+  return num_members == 0 || num_members > BY_BRANCH_MAX_MEMBERS ? 0 : by_branch_passes(num_members);
+}
+
+extern "C" int rf_amd_found_by_branch(rf_amd_engine* e, const uint64_t* d_cand, const uint64_t* d_cand_key,
+                                      const uint64_t* d_count, uint64_t cap, uint32_t num_members, uint32_t* d_order,
+                                      uint64_t* d_order_key, uint64_t* d_branch, uint64_t* d_branch_off,
+                                      uint64_t branch_cap, uint64_t* d_num_branches, void* d_scratch, void* stream) {
+  if (const char* m = by_branch_refusal(e, d_cand, d_cand_key, d_count, cap, num_members, d_order, d_order_key,
+                                        d_branch, d_branch_off, branch_cap, d_num_branches, d_scratch))
+    return fail(RF_AMD_EINVAL, m);
+  HIPCHK(hipSetDevice(e->device));
+  (void)hipGetLastError();
+  return launch_rc("group by branch",
+                   rf_launch_found_by_branch(stream_of(e, stream), d_cand, d_cand_key, d_count, cap, num_members,
+                                             d_order, d_order_key, d_branch, d_branch_off, branch_cap,
+                                             d_num_branches, d_scratch));
 }
 
 // ---- range maps: multi-get keys routed to their member lists --------------------------------

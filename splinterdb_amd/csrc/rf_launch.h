@@ -8,6 +8,7 @@
 #include "rf_range_plan.h"
 #include "rf_range_seg_plan.h"
 #include "rf_per_key_plan.h"
+#include "rf_by_branch_plan.h"
 
 extern "C" {
 
@@ -113,6 +114,18 @@ int rf_launch_found_per_key(void* stream, const uint64_t* found, const uint32_t*
                             uint64_t cap, uint64_t* count, void* scratch);
 // diagnostics (rf_amd_diag_fanout_max_blocks): a cap on both kernels' grids; 0 = none
 void rf_per_key_set_max_blocks(uint32_t blocks);
+
+// ---- group by branch (rf_by_branch.hip) -------------------------------------------------------
+// by_branch_launches(num_members) launches: the first min(*count, cap) records of cand to
+// order[< cap] (their positions, stable by sort key), order_key[t] = cand_key[order[t]] (both
+// nullptr: not written), branch[< branch_cap], branch_off[<= branch_cap] and *num_branches;
+// scratch: by_branch_scratch_bytes(cap, num_members) bytes, 8-byte aligned (rf_by_branch_plan.h)
+int rf_launch_found_by_branch(void* stream, const uint64_t* cand, const uint64_t* cand_key, const uint64_t* count,
+                              uint64_t cap, uint32_t num_members, uint32_t* order, uint64_t* order_key,
+                              uint64_t* branch, uint64_t* branch_off, uint64_t branch_cap, uint64_t* num_branches,
+                              void* scratch);
+// diagnostics (rf_amd_diag_fanout_max_blocks): a cap on the tile kernels' grids; 0 = none
+void rf_by_branch_set_max_blocks(uint32_t blocks);
 
 // ---- estimate, hashing, routing, verify ---------------------------------------------------
 // bitmap (zeroed by the caller, bitmap_words a multiple of 4) -> counters[0] = entries

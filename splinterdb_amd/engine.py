@@ -78,6 +78,8 @@ EXPORTED = [
     "rf_amd_filter_set_exists_keys", "rf_amd_filter_set_exists_var_keys", "rf_amd_filter_set_exists_hashes",
     "rf_amd_filter_set_exists_keys_ragged", "rf_amd_filter_set_exists_var_keys_ragged",
     "rf_amd_filter_set_exists_hashes_ragged",
+    "rf_amd_found_by_branch_scratch_bytes", "rf_amd_found_by_branch",
+    "rf_amd_diag_by_branch_tile", "rf_amd_diag_by_branch_passes",
 ]
 ROUTE_MAX_WORLD = 16
 FOUND_COMPACT_TILE = 4096  # found words per workgroup of rf_amd_found_compact (FC_TILE)
@@ -311,6 +313,13 @@ def load_library(build_if_missing=True):
     L.rf_amd_found_per_key_ragged.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, u64, vp, vp, vp]
     L.rf_amd_diag_per_key_tile.argtypes = []
     L.rf_amd_diag_per_key_tile.restype = u32
+    L.rf_amd_found_by_branch_scratch_bytes.argtypes = [u64, u32]
+    L.rf_amd_found_by_branch_scratch_bytes.restype = u64
+    L.rf_amd_found_by_branch.argtypes = [vp, vp, vp, vp, u64, u32, vp, vp, vp, vp, u64, vp, vp, vp]
+    L.rf_amd_diag_by_branch_tile.argtypes = []
+    L.rf_amd_diag_by_branch_tile.restype = u32
+    L.rf_amd_diag_by_branch_passes.argtypes = [u32]
+    L.rf_amd_diag_by_branch_passes.restype = u32
     L.rf_amd_host_alloc.argtypes = [vp, u64, ctypes.POINTER(vp)]
     L.rf_amd_host_free.argtypes = [vp, vp]
     L.rf_amd_host_free.restype = None
@@ -1089,6 +1098,76 @@ def found_per_key_ragged(d_found, d_member, d_member_off, n, d_key_off, d_cand, 
                    n, d_key_off, d_cand, d_cand_key, d_count, stream, engine)
 
 
+def by_branch_sort_key(cand, num_members):
+    """the 32-bit sort key of rf_amd_found_by_branch for every record: ((c >> 8) & (2^mb - 1)) << 6
+    | (c & 63), mb the bit width of num_members - 1"""
+    if not 1 <= num_members <= 1 << 26:
+        raise ValueError("num_members outside [1, 2^26]")
+    c = np.ascontiguousarray(cand).reshape(-1).view(np.uint64)
+    mask = np.uint64((1 << (num_members - 1).bit_length()) - 1)
+    return ((((c >> np.uint64(8)) & mask) << np.uint64(6)) | (c & np.uint64(63))).astype(np.uint32)
+
+
+def found_by_branch_host(cand, num_members, cand_key=None):
+    """Host mirror of rf_amd_found_by_branch over all of cand (the caller slices the first
+    min(count, cap) records): a numpy stable argsort on the sort key. Returns (order uint32[m],
+    order_key uint64[m] or None, branch uint64[runs], branch_off uint64[runs + 1]): order[t] = the
+    position in cand of the record at grouped position t, order_key = cand_key[order], branch[u]
+    the record of run u's first element, the run being order[branch_off[u] : branch_off[u + 1]]."""
+    c = np.ascontiguousarray(cand).reshape(-1).view(np.uint64)
+    key = by_branch_sort_key(c, num_members)
+    order = np.argsort(key, kind="stable").astype(np.uint32)
+    skey = key[order]
+    heads = np.flatnonzero(np.concatenate(([True], skey[1:] != skey[:-1]))) if c.size else np.zeros(0, np.int64)
+    order_key = None
+    if cand_key is not None:
+        order_key = np.ascontiguousarray(cand_key).reshape(-1).view(np.uint64)[order]
+    branch_off = np.concatenate((heads, [c.size])).astype(np.uint64)
+    return order, order_key, c[order[heads]], branch_off
+
+
+def found_by_branch_scratch_bytes(cap, num_members) -> int:
+    return int(load_library().rf_amd_found_by_branch_scratch_bytes(cap, num_members))
+
+
+def diag_by_branch_tile() -> int:
+    """records per tile of found_by_branch (rf_amd_diag_by_branch_tile)"""
+    return int(load_library().rf_amd_diag_by_branch_tile())
+
+
+def diag_by_branch_passes(num_members) -> int:
+    """digit passes of found_by_branch's sort (rf_amd_diag_by_branch_passes)"""
+    return int(load_library().rf_amd_diag_by_branch_passes(num_members))
+
+
+_by_branch_scratch = {}  # (engine, stream) -> the scratch of the last found_by_branch issued there
+
+
+def found_by_branch(d_cand, d_cand_key, d_count, cap, num_members, d_order, d_order_key, d_branch, d_branch_off,
+                    branch_cap, d_num_branches, stream=None, engine=None):
+    """rf_amd_found_by_branch: the first min(d_count, cap) records of d_cand, as a found_per_key
+    call left them, grouped by branch, asynchronously: d_order (int32 / uint32, cap elements), the
+    optional d_order_key (with d_cand_key; both None: not produced), the first branch_cap runs in
+    d_branch and d_branch_off (branch_cap + 1 elements) and the true number of runs in
+    d_num_branches. The scratch is a torch buffer kept until the next call on the same stream."""
+    import torch
+    eng = engine or default_engine()
+    st = _stream(stream)
+    if cap and d_order.numel() < cap:
+        raise ValueError("d_order is shorter than cap")
+    if d_order_key is not None and d_order_key.numel() < cap:
+        raise ValueError("d_order_key is shorter than cap")
+    if branch_cap and (d_branch.numel() < branch_cap or d_branch_off.numel() < branch_cap + 1):
+        raise ValueError("d_branch / d_branch_off are shorter than branch_cap / branch_cap + 1")
+    scratch = torch.empty(found_by_branch_scratch_bytes(cap, num_members) // 8, dtype=torch.int64,
+                          device=d_count.device)
+    _check(load_library().rf_amd_found_by_branch(eng.h, _dptr(d_cand), _dptr(d_cand_key), _dptr(d_count), cap,
+                                                 num_members, _dptr(d_order), _dptr(d_order_key), _dptr(d_branch),
+                                                 _dptr(d_branch_off), branch_cap, _dptr(d_num_branches),
+                                                 scratch.data_ptr(), st))
+    _by_branch_scratch[(id(eng), st)] = scratch
+
+
 _exists_routed_csr = {}  # (engine, stream) -> the CSR of the last exists_routed issued there
 
 
@@ -1485,6 +1564,46 @@ class FilterSet:
             if count <= size:
                 return d_key_off, d_cand, count, d_cand_key
             size = count
+
+    def group_by_branch(self, per_key_result, stream=None):
+        """found_by_branch on what a multiget_*_per_key method returned, (d_key_off, d_cand, count,
+        d_cand_key), with this set's num_members: returns (d_order int32[count], d_order_key
+        int64[count], d_branch int64[runs], d_branch_off int64[runs + 1], runs). Run u is the
+        records d_cand[d_order[d_branch_off[u] : d_branch_off[u + 1]]] of the branch d_branch[u],
+        in batch order, and d_order_key their keys. The branch table is sized for 64 branches per
+        member, at most one per record; only this step is repeated, into a larger table, when the
+        branches outnumber it (ids at or above num_members can make them)."""
+        return self._group_by_branch(per_key_result, stream, None)
+
+    def _group_by_branch(self, per_key_result, stream, branch_cap):
+        """group_by_branch with the first branch table of branch_cap runs (None: the default)"""
+        import contextlib
+
+        import torch
+        _, d_cand, count, d_cand_key = per_key_result
+        dev = d_cand.device
+        # *d_count is read on the device: its fill runs on the stream of the launches
+        on = torch.cuda.stream(torch.cuda.ExternalStream(stream)) if stream is not None else contextlib.nullcontext()
+        with on:
+            d_count = torch.full((1,), count, dtype=torch.int64, device=dev)
+        d_runs = torch.empty(1, dtype=torch.int64, device=dev)  # every call writes it: no fill to order
+        # never empty: no records is still a buffer, so that the key pointers are both non-NULL
+        d_order = torch.empty(max(1, count), dtype=torch.int32, device=dev)
+        d_order_key = torch.empty(max(1, count), dtype=torch.int64, device=dev)
+        keyed = d_cand_key.numel() > 0  # a per-key call with cap 0 left no key buffer: then neither side's
+        size = max(1, min(count, 64 * self.num_members)) if branch_cap is None else branch_cap
+        while True:
+            d_branch = torch.empty(size, dtype=torch.int64, device=dev)
+            d_branch_off = torch.empty(size + 1, dtype=torch.int64, device=dev)
+            found_by_branch(d_cand, d_cand_key if keyed else None, d_count, count, self.num_members, d_order,
+                            d_order_key if keyed else None, d_branch, d_branch_off, size, d_runs, stream,
+                            self.engine)
+            if stream is not None:  # a raw handle torch's own copy is not ordered with
+                torch.cuda.ExternalStream(stream).synchronize()
+            runs = int(d_runs.item())
+            if runs <= size:
+                return d_order[:count], d_order_key[:count], d_branch[:runs], d_branch_off[:runs + 1], runs
+            size = runs
 
     def _compact_found(self, d_found, n, K, cap, stream):
         """the multi-get's tail: the candidates of d_found[:n * K] as (d_cand, count)"""

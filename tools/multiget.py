@@ -73,6 +73,12 @@ minimum, maximum and median, the parent path's round-to-round spread, and whethe
 median is within that spread of the parent path's. Default output: profiles/multiget_per_key.json
 (profiles/multiget_var_per_key.json).
 
+--by-branch: the per-key records grouped by branch, two ways, on the CSR of the --per-key route call
+and on lists that hold every key's own filter. (parent_path) torch.sort(stable=True) of the sort
+keys, the gather of the records' keys and torch.unique_consecutive(return_counts=True), with their
+synchronisation and allocations. (by_branch) one rf_amd_found_by_branch. Same rounds and condition
+as --per-key; the results are compared before timing. Default output: profiles/multiget_by_branch.json.
+
 --exists: the existence multi-get (SPLINTERDB_LOOKUP_MIGHT_EXIST), on the same two workloads (with
 --var: variable-length keys). (exists) one rf_amd_filter_set_exists_*_ragged: one byte per key.
 (ragged_probe) the parent path's cheapest possible start: the ragged probe alone on the same
@@ -82,7 +88,7 @@ the key's pairs is not zero" before anything is timed; then alternating rounds w
 method and the same condition as --per-key. Default output: profiles/multiget_exists.json
 (profiles/multiget_var_exists.json).
 
-    timeout -k 10 600 python tools/multiget.py [--var] [--ragged | --routed | --per-key | --exists] [--filters 64] [--keys 1048576]
+    timeout -k 10 600 python tools/multiget.py [--var] [--ragged | --routed | --per-key | --by-branch | --exists] [--filters 64] [--keys 1048576]
                                                [--n 16777216] [--k 4] [--rounds 7] [--warmup 2]
                                                [--out profiles/multiget.json]
     timeout -k 10 300 python tools/multiget.py --update --filters 1024 --keys 4096
@@ -447,6 +453,134 @@ def csr_workloads(args, eng, stream, kin, hr):
         return off, member, m
 
     return (("ragged", ragged_csr), ("routed", routed_csr))
+
+
+def by_branch(args, fset, eng, stream, kin, own, timed, rng):
+    """--by-branch: the per-key records grouped by branch, two ways, on the CSR of a route call
+    (the --per-key shape) and on lists that hold every key's own filter, so that every key has at
+    least one record; kin: the keys' arguments, own: the filter that holds key i"""
+    import statistics
+
+    import numpy as np
+    F, n = args.filters, args.n
+    st = stream.cuda_stream
+    dev = kin[0].device
+    hr = np.random.default_rng(13)
+    probe_r = fset.probe_var_keys_ragged if args.var else fset.probe_keys_ragged
+    nm = fset.num_members
+    mask = (1 << (nm - 1).bit_length()) - 1
+    passes = E.diag_by_branch_passes(nm)
+
+    def present_csr():
+        """key i against its own filter and three random ones"""
+        with torch.cuda.stream(stream):
+            g = torch.Generator(device=dev)
+            g.manual_seed(11)
+            member = torch.randint(0, F, (n, 4), device=dev, generator=g).to(torch.int32)
+            member[:, 0] = own.to(torch.int32)
+            off = torch.arange(n + 1, device=dev, dtype=torch.int64) * 4
+        stream.synchronize()
+        return off, member.reshape(-1).contiguous(), 4 * n
+
+    def measure(off, member, m):
+        with torch.cuda.stream(stream):
+            found = torch.zeros(m, dtype=torch.int64, device=dev)
+            d_count = torch.zeros(1, dtype=torch.int64, device=dev)
+            d_key_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+            probe_r(*kin, member, off, n, found, stream=st)
+            E.found_per_key_ragged(found, member, off, n, d_key_off, None, None, d_count, stream=st, engine=eng)
+        stream.synchronize()
+        count = int(d_count.item())
+        bcap = 64 * nm
+        with torch.cuda.stream(stream):
+            d_cand = torch.zeros(max(count, 1), dtype=torch.int64, device=dev)
+            d_cand_key = torch.zeros_like(d_cand)
+            E.found_per_key_ragged(found, member, off, n, d_key_off, d_cand, d_cand_key, d_count, stream=st,
+                                   engine=eng)
+            d_order = torch.zeros(max(count, 1), dtype=torch.int32, device=dev)
+            d_okey = torch.zeros_like(d_cand)
+            d_branch = torch.zeros(bcap, dtype=torch.int64, device=dev)
+            d_boff = torch.zeros(bcap + 1, dtype=torch.int64, device=dev)
+            d_runs = torch.zeros(1, dtype=torch.int64, device=dev)
+        stream.synchronize()
+        del found, d_key_off
+        got = {}
+
+        def sort_key(c):
+            return (((c >> 8) & mask) << 6) | (c & 63)
+
+        def parent_path():  # what a caller had on the device: a stable sort, the gather, the runs
+            skey, order = torch.sort(sort_key(d_cand[:count]), stable=True)
+            got["order"] = order
+            got["order_key"] = d_cand_key[:count][order]
+            got["u"], got["counts"] = torch.unique_consecutive(skey, return_counts=True)
+
+        def by_branch_call():
+            E.found_by_branch(d_cand, d_cand_key, d_count, count, nm, d_order, d_okey, d_branch, d_boff, bcap,
+                              d_runs, stream=st, engine=eng)
+
+        # both ways once, compared before anything is timed
+        with torch.cuda.stream(stream):
+            parent_path()
+            by_branch_call()
+        stream.synchronize()
+        with torch.cuda.stream(stream):
+            runs = int(d_runs.item())
+            assert runs == got["u"].numel() <= bcap, "the numbers of runs differ"
+            assert torch.equal(d_order[:count].to(torch.int64), got["order"]), "order differs from torch.sort"
+            assert torch.equal(d_okey[:count], got["order_key"]), "keys differ from the gather"
+            starts = torch.cumsum(got["counts"], 0) - got["counts"]
+            assert torch.equal(d_boff[:runs], starts) and int(d_boff[runs].item()) == count, "run starts differ"
+            assert torch.equal(sort_key(d_branch[:runs]), got["u"]), "branches differ from unique_consecutive"
+            del starts
+        stream.synchronize()
+        ways = {"parent_path": parent_path, "by_branch": by_branch_call}
+        t = {w: [] for w in ways}
+        for r in range(args.warmup + args.rounds):
+            for w, fn in ways.items():  # alternating: one of each per round
+                ms = timed(fn)
+                if r >= args.warmup:
+                    t[w].append(ms)
+        a, b = t["parent_path"], t["by_branch"]
+        spread = max(a) - min(a)
+        return {
+            "pairs": m, "records": count, "records_per_key": round(count / n, 4), "branches": runs,
+            "num_members": nm, "passes": passes,
+            "ms": {w: dict(rng(v), median=round(statistics.median(v), 4)) for w, v in t.items()},
+            "parent_spread_ms": round(spread, 4),
+            # the condition: the new call's median is not above the parent path's by more than that
+            # path's own round-to-round spread
+            "by_branch_within_parent_spread": bool(statistics.median(b) <= statistics.median(a) + spread),
+            "ranges_touch": not (max(a) < min(b) or max(b) < min(a)),
+            "by_branch_faster_beyond_ranges": bool(max(b) < min(a)),
+            "by_branch_slower_beyond_ranges": bool(max(a) < min(b)),
+            # the new call, per record: each pass reads it twice (8 + 8) and all but the last write the
+            # pair (8); the last writes order and sort key (4 + 4) and gathers the key (8 + 8); the run
+            # table reads the sort keys twice (4 + 4)
+            "by_branch_algorithmic_bytes": count * (24 * passes + 24),
+        }
+
+    out = {
+        "what": ("the records of a per-key multi-get of n %s grouped by branch, two ways: (parent_path) "
+                 "torch.sort(stable=True) of the sort keys, the gather of the records' keys, "
+                 "torch.unique_consecutive(return_counts=True), its synchronisation and allocations included; "
+                 "(by_branch) one rf_amd_found_by_branch; on the CSR of a route call through a map of R lists of "
+                 "min(16, 1 + Geometric(1/3)) random members (3 %% non-zero words) and on lists of each key's own "
+                 "filter and three random ones (every key present); alternating rounds in one process, HIP events "
+                 "on the launch stream" % ("variable-length keys (keys.var_keys, 8-100 B)" if args.var
+                                           else "24-byte keys")),
+        "config": {"filters": F, "keys_per_filter": args.keys, "n": n, "ranges": ROUTED_R, "rounds": args.rounds,
+                   "warmup": args.warmup, "fingerprint_size": 26, "log_index_size": 8},
+    }
+    for name, csr in csr_workloads(args, eng, stream, kin, hr) + (("present", present_csr),):
+        off, member, m = csr()  # the --ragged lists are drawn too, so that the route call's are --per-key's
+        if name != "ragged":
+            out[name] = measure(off, member, m)
+        del off, member
+    out["verified"] = ("before timing, on both workloads: the numbers of runs equal; d_order equal to torch.sort's "
+                       "indices; d_order_key equal to the gather; the run starts equal to the exclusive sums of "
+                       "unique_consecutive's counts; the sort keys of d_branch equal to its values")
+    return out
 
 
 def per_key(args, fset, eng, stream, kin, timed, rng):
@@ -961,6 +1095,8 @@ def main():
                     help="route + ragged probe + compaction from raw keys through a range map")
     ap.add_argument("--per-key", dest="per_key", action="store_true",
                     help="rf_amd_found_per_key_ragged against found_compact + searchsorted + gather")
+    ap.add_argument("--by-branch", dest="by_branch", action="store_true",
+                    help="rf_amd_found_by_branch against torch.sort + gather + unique_consecutive")
     ap.add_argument("--exists", action="store_true",
                     help="rf_amd_filter_set_exists_*_ragged against the ragged probe alone")
     ap.add_argument("--update", action="store_true",
@@ -971,7 +1107,7 @@ def main():
     args = ap.parse_args()
     if args.out is None:
         name = "multiget" + ("_var" if args.var else "") + ("_ragged" if args.ragged else "") + \
-            ("_routed" if args.routed else "") + ("_per_key" if args.per_key else "") + \
+            ("_routed" if args.routed else "") + ("_per_key" if args.per_key else "") + ("_by_branch" if args.by_branch else "") + \
             ("_exists" if args.exists else "") + ".json"
         name = "multiget_update.json" if args.update else "range_segments.json" if args.segments else name
         args.out = os.path.join(ROOT, "profiles", name)
@@ -1054,10 +1190,12 @@ def main():
     def rng(v):
         return {"min": round(min(v), 4), "max": round(max(v), 4), "rounds": [round(x, 4) for x in v]}
 
-    if args.ragged or args.routed or args.per_key or args.exists:
+    if args.ragged or args.routed or args.per_key or args.exists or args.by_branch:
         del found_a, found_b, member
         kin = (d_bytes, d_offs) if args.var else (keys, 24)
-        if args.exists:
+        if args.by_branch:
+            out = by_branch(args, fset, eng, stream, kin, own, timed, rng)
+        elif args.exists:
             out = exists(args, fset, eng, stream, kin, timed, rng)
         elif args.per_key:
             out = per_key(args, fset, eng, stream, kin, timed, rng)
