@@ -437,6 +437,48 @@ int rf_amd_found_by_branch(rf_amd_engine *e, const uint64_t *d_cand, const uint6
                            uint32_t *d_order, uint64_t *d_order_key,
                            uint64_t *d_branch, uint64_t *d_branch_off, uint64_t branch_cap,
                            uint64_t *d_num_branches, void *d_scratch, void *stream);
+/* the stepwise hand-out: the early exit of the lookup loop for a consumer that walks the B-trees
+ * branch by branch. The reference walks a key's candidates newest first and stops at the first
+ * definitive message (trunk_ondisk_bundle_merge_lookup, src/trunk.c:6057-6087, out at :6085 on
+ * lookup_result_should_continue, src/lookup_result.h:150-156; :6310 and :6328 between bundles and
+ * nodes). This call hands out, for every key whose lookup is still open, its next `width`
+ * records, in batch order and in exactly the form rf_amd_found_by_branch takes; the consumer
+ * alternates advance, group by branch, walk the trees, mark keys done, until a call's
+ * *d_out_count is 0. With width 1 it does the branch lookups of the reference's loop and none
+ * after a definitive hit.
+ * d_key_off (n + 1 words), d_cand and cand_cap are what a rf_amd_found_per_key* call wrote and was
+ * given; records at or past cand_cap do not exist. d_cursor[i] (n uint32) is the number of key
+ * i's records already handed out; the caller owns it between calls. d_done is optional (NULL:
+ * every key is open): n bytes at any alignment, a non-zero byte means key i's lookup is complete;
+ * the consumer writes it between calls. flags: RF_AMD_ADVANCE_FIRST -- the cursors count as 0 and
+ * are not read; all n are written.
+ * For key i ascending: a = d_key_off[i] + d_cursor[i], e = min(d_key_off[i+1], cand_cap); take_i =
+ * 0 if the key is done or a >= e, else min(width, e - a, 65,535 * 64) (the last term keeps a
+ * tile's 32-bit count from overflowing on offsets the call does not validate). The output is the
+ * concatenation over i of d_cand[a .. a + take_i); d_out_key (optional, NULL: not written)
+ * receives the key index i of every record, the type and meaning of d_cand_key. *d_out_count =
+ * the sum of take_i, the true total, also when it exceeds out_cap. Only positions below out_cap
+ * are written: nothing at or past d_out_cand[out_cap) or d_out_key[out_cap). d_cursor[i] advances
+ * by the number of key i's records written, so a key cut by out_cap gets the rest in the next
+ * call and nothing is lost. A cursor that does not advance keeps its value (0 under FIRST);
+ * nothing outside d_cursor[0, n) is written.
+ * rf_amd_found_by_branch(e, d_out_cand, d_out_key, d_out_count, out_cap, ...) chains behind it
+ * with no host read.
+ * Asynchronous on stream (NULL = the engine's), three launches whatever n is, no allocation, no
+ * synchronisation, no atomics on global memory, no workgroup waits for another; the same input
+ * gives the same bytes. d_scratch (8-byte aligned) holds rf_amd_found_advance_scratch_bytes(n)
+ * bytes (callable without a device; non-decreasing in n; a multiple of 8; never 0). n == 0 writes
+ * *d_out_count = 0 and nothing else.
+ * EINVAL: a NULL engine; n >= 2^56; width == 0; unknown flag bits; a NULL d_out_count; a NULL
+ * d_out_cand with out_cap > 0; a scratch that is not 8-byte aligned; with n > 0 a NULL d_key_off,
+ * d_cursor or d_scratch, and a NULL d_cand with cand_cap > 0. */
+#define RF_AMD_ADVANCE_FIRST 1u   /* cursors count as 0 and are not read; they are written */
+uint64_t rf_amd_found_advance_scratch_bytes(uint64_t n);
+int rf_amd_found_advance(rf_amd_engine *e, const uint64_t *d_key_off, const uint64_t *d_cand,
+                         uint64_t cand_cap, uint64_t n, uint32_t width, uint32_t flags,
+                         const uint8_t *d_done, uint32_t *d_cursor,
+                         uint64_t *d_out_cand, uint64_t *d_out_key, uint64_t out_cap,
+                         uint64_t *d_out_count, void *d_scratch, void *stream);
 /* ---- range maps: multi-get keys routed to their member lists on the device ----------------
  * What produces the ragged probe's per-key lists. At each node on its trunk path a key takes
  * the last pivot whose key is <= it (trunk_ondisk_node_find_pivot, src/trunk.c:5886-5932,

@@ -117,7 +117,8 @@ uint32_t rf_amd_diag_range_seg_launch_ids(void);
  * a wave: a test takes lists of exactly this length and of one id more */
 uint32_t rf_amd_diag_range_seg_thread_ids(void);
 /* the keys of one tile of rf_amd_found_per_key / _ragged (the unit of their scratch and of their
- * grid-stride loops, which honour rf_amd_diag_fanout_max_blocks like the route kernels) */
+ * grid-stride loops, which honour rf_amd_diag_fanout_max_blocks like the route kernels);
+ * rf_amd_found_advance walks its keys in the same tiles and honours the same cap */
 uint32_t rf_amd_diag_per_key_tile(void);
 /* the records of one tile of rf_amd_found_by_branch (the unit of its scratch and of its
  * grid-stride loops, which honour rf_amd_diag_fanout_max_blocks too), and the digit passes of its

@@ -2323,6 +2323,7 @@ extern "C" int rf_amd_diag_fanout_max_blocks(uint32_t blocks) {
   rf_range_set_max_blocks(blocks);
   rf_per_key_set_max_blocks(blocks);
   rf_by_branch_set_max_blocks(blocks);
+  rf_advance_set_max_blocks(blocks);
   return 0;
 }
 
@@ -2400,6 +2401,27 @@ extern "C" int rf_amd_found_by_branch(rf_amd_engine* e, const uint64_t* d_cand, 
                    rf_launch_found_by_branch(stream_of(e, stream), d_cand, d_cand_key, d_count, cap, num_members,
                                              d_order, d_order_key, d_branch, d_branch_off, branch_cap,
                                              d_num_branches, d_scratch));
+}
+
+// ---- stepwise hand-out: each open key's next records, in the form the grouping takes ----------
+// The sizing and the argument checks are rf_advance_plan.h's, the kernels rf_advance.hip's.
+static_assert(ADVANCE_FIRST == RF_AMD_ADVANCE_FIRST, "the plan's flag is the header's");
+extern "C" uint64_t rf_amd_found_advance_scratch_bytes(uint64_t n) { return advance_scratch_bytes(n); }
+
+extern "C" int rf_amd_found_advance(rf_amd_engine* e, const uint64_t* d_key_off, const uint64_t* d_cand,
+                                    uint64_t cand_cap, uint64_t n, uint32_t width, uint32_t flags,
+                                    const uint8_t* d_done, uint32_t* d_cursor, uint64_t* d_out_cand,
+                                    uint64_t* d_out_key, uint64_t out_cap, uint64_t* d_out_count, void* d_scratch,
+                                    void* stream) {
+  if (const char* m = advance_refusal(e, d_key_off, d_cand, cand_cap, n, width, flags, d_cursor, d_out_cand, out_cap,
+                                      d_out_count, d_scratch))
+    return fail(RF_AMD_EINVAL, m);
+  HIPCHK(hipSetDevice(e->device));
+  (void)hipGetLastError();
+  return launch_rc("stepwise hand-out",
+                   rf_launch_found_advance(stream_of(e, stream), d_key_off, d_cand, cand_cap, n, width,
+                                           (flags & ADVANCE_FIRST) != 0, d_done, d_cursor, d_out_cand, d_out_key,
+                                           out_cap, d_out_count, d_scratch));
 }
 
 // ---- range maps: multi-get keys routed to their member lists --------------------------------

@@ -9,6 +9,7 @@
 #include "rf_range_seg_plan.h"
 #include "rf_per_key_plan.h"
 #include "rf_by_branch_plan.h"
+#include "rf_advance_plan.h"
 
 extern "C" {
 
@@ -126,6 +127,20 @@ int rf_launch_found_by_branch(void* stream, const uint64_t* cand, const uint64_t
                               void* scratch);
 // diagnostics (rf_amd_diag_fanout_max_blocks): a cap on the tile kernels' grids; 0 = none
 void rf_by_branch_set_max_blocks(uint32_t blocks);
+
+// ---- stepwise hand-out (rf_advance.hip) -------------------------------------------------------
+// k_advance_count, k_range_scan, k_advance_emit: for each of the n keys that is not done (done ==
+// nullptr: none is) the next min(width, ...) records of cand[key_off[i] + cursor[i] ..) below
+// min(key_off[i + 1], cand_cap) (advance_take, rf_advance_plan.h; first: every cursor counts as 0)
+// to out_cand[< out_cap] and out_key[< out_cap] (nullptr: not written), the true total to
+// *out_count, cursor[i] += the records written; scratch: advance_scratch_bytes(n) bytes, 8-byte
+// aligned
+int rf_launch_found_advance(void* stream, const uint64_t* key_off, const uint64_t* cand, uint64_t cand_cap,
+                            uint64_t n, uint32_t width, int first, const uint8_t* done, uint32_t* cursor,
+                            uint64_t* out_cand, uint64_t* out_key, uint64_t out_cap, uint64_t* out_count,
+                            void* scratch);
+// diagnostics (rf_amd_diag_fanout_max_blocks): a cap on both kernels' grids; 0 = none
+void rf_advance_set_max_blocks(uint32_t blocks);
 
 // ---- estimate, hashing, routing, verify ---------------------------------------------------
 // bitmap (zeroed by the caller, bitmap_words a multiple of 4) -> counters[0] = entries

@@ -80,6 +80,7 @@ EXPORTED = [
     "rf_amd_filter_set_exists_hashes_ragged",
     "rf_amd_found_by_branch_scratch_bytes", "rf_amd_found_by_branch",
     "rf_amd_diag_by_branch_tile", "rf_amd_diag_by_branch_passes",
+    "rf_amd_found_advance_scratch_bytes", "rf_amd_found_advance",
 ]
 ROUTE_MAX_WORLD = 16
 FOUND_COMPACT_TILE = 4096  # found words per workgroup of rf_amd_found_compact (FC_TILE)
@@ -320,6 +321,9 @@ def load_library(build_if_missing=True):
     L.rf_amd_diag_by_branch_tile.restype = u32
     L.rf_amd_diag_by_branch_passes.argtypes = [u32]
     L.rf_amd_diag_by_branch_passes.restype = u32
+    L.rf_amd_found_advance_scratch_bytes.argtypes = [u64]
+    L.rf_amd_found_advance_scratch_bytes.restype = u64
+    L.rf_amd_found_advance.argtypes = [vp, vp, vp, u64, u64, u32, u32, vp, vp, vp, vp, u64, vp, vp, vp]
     L.rf_amd_host_alloc.argtypes = [vp, u64, ctypes.POINTER(vp)]
     L.rf_amd_host_free.argtypes = [vp, vp]
     L.rf_amd_host_free.restype = None
@@ -1168,6 +1172,129 @@ def found_by_branch(d_cand, d_cand_key, d_count, cap, num_members, d_order, d_or
     _by_branch_scratch[(id(eng), st)] = scratch
 
 
+ADVANCE_FIRST = 1  # RF_AMD_ADVANCE_FIRST: the cursors count as 0 and are not read; they are written
+ADVANCE_MAX_TAKE = 65535 * 64  # the records one key takes in one call at most (PER_KEY_MAX_KEY_CANDS)
+
+
+def found_advance_host(key_off, cand, cand_cap, width, done, cursor, out_cap):
+    """Host mirror of rf_amd_found_advance: key_off the n + 1 record offsets and cand the records
+    of a found_per_key call, cand_cap the capacity that call was given, done n bytes or None
+    (every key open), cursor n uint32 or None (RF_AMD_ADVANCE_FIRST: all 0). Returns (out_cand
+    uint64[w], out_key uint64[w], count, new_cursor uint32[n]) with w = min(count, out_cap) the
+    records written and count the true total."""
+    off = np.ascontiguousarray(key_off).reshape(-1).view(np.uint64).astype(np.int64)
+    n = off.size - 1
+    c = np.ascontiguousarray(cand).reshape(-1).view(np.uint64)
+    cur = np.zeros(n, dtype=np.int64) if cursor is None else \
+        np.ascontiguousarray(cursor).reshape(-1).view(np.uint32).astype(np.int64)
+    if not 1 <= width < 1 << 32:
+        raise ValueError("width outside [1, 2^32)")
+    a = off[:-1] + cur
+    e = np.minimum(off[1:], cand_cap)
+    take = np.clip(np.minimum(e - a, min(width, ADVANCE_MAX_TAKE)), 0, None)
+    if done is not None:
+        take[np.ascontiguousarray(done).reshape(-1).view(np.uint8) != 0] = 0
+    pos = np.cumsum(take) - take  # key i's first output position
+    count = int(take.sum())
+    wr = np.clip(out_cap - pos, 0, take)  # the records of key i below out_cap
+    new_cursor = cur + wr
+    out_key = np.repeat(np.arange(n, dtype=np.int64), wr)
+    src = np.arange(out_key.size, dtype=np.int64) - pos[out_key] + a[out_key]
+    return c[src], out_key.astype(np.uint64), count, new_cursor.astype(np.uint32)
+
+
+def found_advance_scratch_bytes(n) -> int:
+    return int(load_library().rf_amd_found_advance_scratch_bytes(n))
+
+
+_advance_scratch = {}  # (engine, stream) -> the scratch of the last found_advance issued there
+
+
+def found_advance(d_key_off, d_cand, cand_cap, n, width, flags, d_done, d_cursor, d_out_cand, d_out_key, out_cap,
+                  d_out_count, stream=None, engine=None):
+    """rf_amd_found_advance: for every key that is not done (d_done uint8[n] or None) the next
+    `width` records of d_cand behind its cursor (d_cursor int32 / uint32[n]; flags ADVANCE_FIRST:
+    taken as 0) into d_out_cand and d_out_key (None: not written), both of out_cap elements, the
+    true total into d_out_count, the cursors advanced by what was written, asynchronously.
+    d_key_off, d_cand and cand_cap are a found_per_key call's. The scratch is a torch buffer kept
+    until the next call on the same stream."""
+    import torch
+    eng = engine or default_engine()
+    st = _stream(stream)
+    for name, buf in (("d_out_cand", d_out_cand), ("d_out_key", d_out_key)):
+        if buf is not None and not isinstance(buf, int) and buf.numel() < out_cap:
+            raise ValueError(f"{name} is shorter than out_cap")
+    scratch = torch.empty(found_advance_scratch_bytes(n) // 8, dtype=torch.int64, device=d_out_count.device)
+    _check(load_library().rf_amd_found_advance(eng.h, _dptr(d_key_off), _dptr(d_cand), cand_cap, n, width, flags,
+                                               _dptr(d_done), _dptr(d_cursor), _dptr(d_out_cand), _dptr(d_out_key),
+                                               out_cap, _dptr(d_out_count), scratch.data_ptr(), st))
+    _advance_scratch[(id(eng), st)] = scratch
+
+
+class LookupSteps:
+    """A multi-get with the early exit of the reference's loop (FilterSet.lookup_steps): every
+    step() hands out the next `width` records of each key that is still open."""
+
+    def __init__(self, fset, per_key_result, width=1, stream=None):
+        import torch
+        if not 1 <= width < 1 << 32:
+            raise ValueError("width outside [1, 2^32)")
+        self.fset, self.width, self.stream = fset, width, stream
+        self.d_key_off, self.d_cand, count, _ = per_key_result
+        self.n = self.d_key_off.numel() - 1
+        self.cand_cap = min(count, self.d_cand.numel())
+        dev = self.d_key_off.device
+        # a step hands out at most width records per key and never more than there are: no cut
+        self.out_cap = max(1, min(self.cand_cap, self.n * width))
+        self.d_cursor = torch.empty(max(1, self.n), dtype=torch.int32, device=dev)  # the first step writes it
+        self.d_out_cand = torch.empty(self.out_cap, dtype=torch.int64, device=dev)
+        self.d_out_key = torch.empty(self.out_cap, dtype=torch.int64, device=dev)
+        self.d_out_count = torch.empty(1, dtype=torch.int64, device=dev)
+        self.d_order = torch.empty(self.out_cap, dtype=torch.int32, device=dev)
+        self.d_order_key = torch.empty(self.out_cap, dtype=torch.int64, device=dev)
+        self.d_runs = torch.empty(1, dtype=torch.int64, device=dev)
+        self.branch_cap = max(1, min(self.out_cap, 64 * fset.num_members))
+        self.steps = 0
+
+    def _sync(self):
+        if self.stream is not None:  # a raw handle torch's own copy is not ordered with
+            import torch
+            torch.cuda.ExternalStream(self.stream).synchronize()
+
+    def step(self, d_done=None, by_branch=True):
+        """One advance: d_done (uint8 / bool [n], or None) marks the keys whose lookup is
+        complete. Returns (d_out_cand, d_out_key, count, group): the count records handed out and
+        their keys, in batch order, and with by_branch what FilterSet.group_by_branch returns
+        for them, (d_order, d_order_key, d_branch, d_branch_off, runs), else None -- the grouping
+        is issued behind the advance and reads its count on the device. count == 0: the multi-get
+        has finished. The tensors are views of buffers that the next step overwrites."""
+        import torch
+        eng = self.fset.engine
+        found_advance(self.d_key_off, self.d_cand, self.cand_cap, self.n, self.width,
+                      0 if self.steps else ADVANCE_FIRST, d_done, self.d_cursor, self.d_out_cand, self.d_out_key,
+                      self.out_cap, self.d_out_count, self.stream, eng)
+        self.steps += 1
+        group = None
+        while by_branch:
+            d_branch = torch.empty(self.branch_cap, dtype=torch.int64, device=self.d_out_cand.device)
+            d_branch_off = torch.empty(self.branch_cap + 1, dtype=torch.int64, device=self.d_out_cand.device)
+            found_by_branch(self.d_out_cand, self.d_out_key, self.d_out_count, self.out_cap, self.fset.num_members,
+                            self.d_order, self.d_order_key, d_branch, d_branch_off, self.branch_cap, self.d_runs,
+                            self.stream, eng)
+            self._sync()
+            runs = int(self.d_runs.item())
+            if runs <= self.branch_cap:
+                group = (d_branch, d_branch_off, runs)
+                break
+            self.branch_cap = runs  # ids at or above num_members: only the grouping is repeated
+        self._sync()
+        count = int(self.d_out_count.item())
+        if group is not None:
+            d_branch, d_branch_off, runs = group
+            group = (self.d_order[:count], self.d_order_key[:count], d_branch[:runs], d_branch_off[:runs + 1], runs)
+        return self.d_out_cand[:count], self.d_out_key[:count], count, group
+
+
 _exists_routed_csr = {}  # (engine, stream) -> the CSR of the last exists_routed issued there
 
 
@@ -1604,6 +1731,14 @@ class FilterSet:
             if runs <= size:
                 return d_order[:count], d_order_key[:count], d_branch[:runs], d_branch_off[:runs + 1], runs
             size = runs
+
+    def lookup_steps(self, per_key_result, width=1, stream=None):
+        """The early exit of the reference's lookup loop (src/trunk.c:6085) over what a
+        multiget_*_per_key method returned: a LookupSteps whose step(d_done=None, by_branch=True)
+        runs one found_advance -- the next `width` records of every key not marked in d_done --
+        and, with by_branch, found_by_branch behind it. The consumer walks the runs, marks the
+        keys that met a definitive message and steps again until the count is 0."""
+        return LookupSteps(self, per_key_result, width, stream)
 
     def _compact_found(self, d_found, n, K, cap, stream):
         """the multi-get's tail: the candidates of d_found[:n * K] as (d_cand, count)"""

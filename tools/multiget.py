@@ -79,6 +79,13 @@ keys, the gather of the records' keys and torch.unique_consecutive(return_counts
 synchronisation and allocations. (by_branch) one rf_amd_found_by_branch. Same rounds and condition
 as --per-key; the results are compared before timing. Default output: profiles/multiget_by_branch.json.
 
+--advance: one step of the multi-get with early exit, two ways, on the two --by-branch workloads
+and on lists of eight that name each key's own filter four times. (parent_path) torch masks, cumsum,
+repeat_interleave and the gather, with their synchronisation and allocations. (advance) one
+rf_amd_found_advance at width 1. Same rounds and condition as --per-key; the results are compared
+before timing. Then whole multi-gets at width 1, 2 and 4, a key being done at its own filter's
+record: the records handed out against all records. Default output: profiles/multiget_advance.json.
+
 --exists: the existence multi-get (SPLINTERDB_LOOKUP_MIGHT_EXIST), on the same two workloads (with
 --var: variable-length keys). (exists) one rf_amd_filter_set_exists_*_ragged: one byte per key.
 (ragged_probe) the parent path's cheapest possible start: the ragged probe alone on the same
@@ -88,7 +95,7 @@ the key's pairs is not zero" before anything is timed; then alternating rounds w
 method and the same condition as --per-key. Default output: profiles/multiget_exists.json
 (profiles/multiget_var_exists.json).
 
-    timeout -k 10 600 python tools/multiget.py [--var] [--ragged | --routed | --per-key | --by-branch | --exists] [--filters 64] [--keys 1048576]
+    timeout -k 10 600 python tools/multiget.py [--var] [--ragged | --routed | --per-key | --by-branch | --advance | --exists] [--filters 64] [--keys 1048576]
                                                [--n 16777216] [--k 4] [--rounds 7] [--warmup 2]
                                                [--out profiles/multiget.json]
     timeout -k 10 300 python tools/multiget.py --update --filters 1024 --keys 4096
@@ -580,6 +587,176 @@ def by_branch(args, fset, eng, stream, kin, own, timed, rng):
     out["verified"] = ("before timing, on both workloads: the numbers of runs equal; d_order equal to torch.sort's "
                        "indices; d_order_key equal to the gather; the run starts equal to the exclusive sums of "
                        "unique_consecutive's counts; the sort keys of d_branch equal to its values")
+    return out
+
+
+def advance(args, fset, eng, stream, kin, own, timed, rng):
+    """--advance: one step of the early-exit multi-get, two ways, on the CSR of a route call (the
+    --per-key shape), on lists that hold every key's own filter and three random ones, and on
+    lists of eight that name the own filter four times (a key that lives in four bundles of its
+    path); then the records a whole multi-get hands to the consumer at width 1, 2 and 4 against all
+    the records, which is what found_by_branch groups without the exit. kin: the keys' arguments,
+    own: the filter that holds key i"""
+    import statistics
+
+    import numpy as np
+    F, n = args.filters, args.n
+    st = stream.cuda_stream
+    dev = kin[0].device
+    hr = np.random.default_rng(13)
+    probe_r = fset.probe_var_keys_ragged if args.var else fset.probe_keys_ragged
+
+    def present_csr(k, own_at):
+        """key i against k members, its own filter at the places own_at and random ones elsewhere"""
+        def make():
+            with torch.cuda.stream(stream):
+                g = torch.Generator(device=dev)
+                g.manual_seed(11)
+                member = torch.randint(0, F, (n, k), device=dev, generator=g).to(torch.int32)
+                for j in own_at:
+                    member[:, j] = own.to(torch.int32)
+                off = torch.arange(n + 1, device=dev, dtype=torch.int64) * k
+            stream.synchronize()
+            return off, member.reshape(-1).contiguous(), k * n
+        return make
+
+    def measure(off, member, m):
+        with torch.cuda.stream(stream):
+            found = torch.zeros(m, dtype=torch.int64, device=dev)
+            d_count = torch.zeros(1, dtype=torch.int64, device=dev)
+            d_key_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+            probe_r(*kin, member, off, n, found, stream=st)
+            E.found_per_key_ragged(found, member, off, n, d_key_off, None, None, d_count, stream=st, engine=eng)
+        stream.synchronize()
+        count = int(d_count.item())
+        with torch.cuda.stream(stream):
+            d_cand = torch.zeros(max(count, 1), dtype=torch.int64, device=dev)
+            E.found_per_key_ragged(found, member, off, n, d_key_off, d_cand, None, d_count, stream=st, engine=eng)
+            d_done = torch.zeros(n, dtype=torch.uint8, device=dev)
+            d_cursor = torch.zeros(n, dtype=torch.int32, device=dev)
+            zero_cursor = torch.zeros(n, dtype=torch.int32, device=dev)
+            out_cap = max(1, min(count, 4 * n))  # the widest step below
+            d_out = torch.zeros(out_cap, dtype=torch.int64, device=dev)
+            d_out_key = torch.zeros(out_cap, dtype=torch.int64, device=dev)
+            d_out_count = torch.zeros(1, dtype=torch.int64, device=dev)
+            ar = torch.arange(n, device=dev, dtype=torch.int64)
+        stream.synchronize()
+        del found
+        got = {}
+
+        def parent_path(width=1, cursor=zero_cursor, done=d_done):
+            # what a caller had on the device: masks, a cumsum, repeat_interleave (which waits for the
+            # total) and the gather, every step into fresh tensors
+            a = d_key_off[:-1] + cursor
+            e = torch.clamp(d_key_off[1:], max=count)
+            take = torch.clamp(torch.clamp(e - a, max=width), min=0) * (done == 0)
+            pos = torch.cumsum(take, 0) - take
+            key = torch.repeat_interleave(ar, take)
+            src = torch.arange(key.numel(), device=dev, dtype=torch.int64) - pos[key] + a[key]
+            got["cand"], got["key"], got["cursor"] = d_cand[src], key, (cursor + take).to(torch.int32)
+
+        def advance_call(width=1, flags=E.ADVANCE_FIRST, done=d_done):
+            E.found_advance(d_key_off, d_cand, count, n, width, flags, done, d_cursor, d_out, d_out_key, out_cap,
+                            d_out_count, stream=st, engine=eng)
+
+        # both ways once, on the first step and on a later one, compared before anything is timed
+        with torch.cuda.stream(stream):
+            g = torch.Generator(device=dev)
+            g.manual_seed(5)
+            some_done = (torch.rand(n, device=dev, generator=g) < 0.5).to(torch.uint8)
+            one = torch.ones(n, dtype=torch.int32, device=dev)
+        for width, flags, cursor, done in ((1, E.ADVANCE_FIRST, zero_cursor, d_done), (2, 0, one, some_done)):
+            with torch.cuda.stream(stream):
+                d_cursor.copy_(cursor)
+                parent_path(width, cursor, done)
+                advance_call(width, flags, done)
+            stream.synchronize()
+            with torch.cuda.stream(stream):
+                k = int(d_out_count.item())
+                assert k == got["key"].numel() <= out_cap, "the totals differ"
+                assert torch.equal(d_out[:k], got["cand"]), "records differ from the gather"
+                assert torch.equal(d_out_key[:k], got["key"]), "keys differ from repeat_interleave"
+                assert torch.equal(d_cursor, got["cursor"]), "cursors differ"
+            stream.synchronize()
+        del some_done, one
+        first_step = int((d_key_off[1:] > d_key_off[:-1]).sum().item())
+        ways = {"parent_path": parent_path, "advance": advance_call}
+        t = {w: [] for w in ways}
+        for r in range(args.warmup + args.rounds):
+            for w, fn in ways.items():  # alternating: one of each per round
+                ms = timed(fn)
+                if r >= args.warmup:
+                    t[w].append(ms)
+        got.clear()
+
+        def whole_multiget(width):
+            """advance, mark the keys whose step held their own filter, until nothing is handed out"""
+            handed, steps = 0, 0
+            with torch.cuda.stream(stream):
+                d_done.zero_()
+            while True:
+                with torch.cuda.stream(stream):
+                    advance_call(width, 0 if steps else E.ADVANCE_FIRST)
+                stream.synchronize()
+                k = int(d_out_count.item())
+                if k == 0:
+                    break
+                with torch.cuda.stream(stream):
+                    keys_out = d_out_key[:k]
+                    hit = (d_out[:k] >> 8) == own[keys_out]
+                    d_done[keys_out[hit]] = 1
+                stream.synchronize()
+                handed, steps = handed + k, steps + 1
+            return {"records_handed_out": handed, "steps": steps,
+                    "of_all_records": round(handed / max(count, 1), 4)}
+
+        exits = {"width_%d" % w: whole_multiget(w) for w in (1, 2, 4)}
+        a, b = t["parent_path"], t["advance"]
+        spread = max(a) - min(a)
+        return {
+            "pairs": m, "records": count, "records_per_key": round(count / n, 4),
+            "records_in_the_timed_step": first_step,
+            "ms": {w: dict(rng(v), median=round(statistics.median(v), 4)) for w, v in t.items()},
+            "parent_spread_ms": round(spread, 4),
+            # the condition: the new call's median is not above the parent path's by more than that
+            # path's own round-to-round spread
+            "advance_within_parent_spread": bool(statistics.median(b) <= statistics.median(a) + spread),
+            "ranges_touch": not (max(a) < min(b) or max(b) < min(a)),
+            "advance_faster_beyond_ranges": bool(max(b) < min(a)),
+            "advance_slower_beyond_ranges": bool(max(a) < min(b)),
+            # the new call under FIRST: both kernels read two offsets and the done byte per key (the
+            # neighbour's offset comes from the same lines: 8 + 1, twice), the emit writes the cursor (4)
+            # and per record reads it and writes it and its key (8 + 8 + 8)
+            "advance_algorithmic_bytes": n * (2 * 9 + 4) + first_step * 24,
+            # found_by_branch without the exit groups all `records`; with it, what the steps hand out
+            "whole_multiget_with_early_exit": exits,
+        }
+
+    out = {
+        "what": ("one step of a per-key multi-get of n %s with early exit, two ways: (parent_path) torch masks, "
+                 "cumsum, repeat_interleave and the gather, its synchronisation and allocations included; (advance) "
+                 "one rf_amd_found_advance at width 1 under RF_AMD_ADVANCE_FIRST with a done buffer of zeros, so "
+                 "that every round starts from the same cursors; on the CSR of a route call through a map of R "
+                 "lists of min(16, 1 + Geometric(1/3)) random members (3 %% non-zero words), on lists of each "
+                 "key's own filter and three random ones (every key present), and on lists of eight that name "
+                 "the own filter at the places 0, 2, 4 and 6 (every key present in 4 of its members); "
+                 "alternating rounds in one process, HIP events on the launch stream. Then whole multi-gets "
+                 "at width 1, 2 and 4, a key being done when a step held a record of its own filter: the "
+                 "records handed to the consumer against all records" % (
+                     "variable-length keys (keys.var_keys, 8-100 B)" if args.var else "24-byte keys")),
+        "config": {"filters": F, "keys_per_filter": args.keys, "n": n, "ranges": ROUTED_R, "rounds": args.rounds,
+                   "warmup": args.warmup, "fingerprint_size": 26, "log_index_size": 8},
+    }
+    shapes = csr_workloads(args, eng, stream, kin, hr) + (("present", present_csr(4, (0,))),
+                                                          ("present_in_4", present_csr(8, (0, 2, 4, 6))))
+    for name, csr in shapes:
+        off, member, m = csr()  # the --ragged lists are drawn too, so that the route call's are --per-key's
+        if name != "ragged":
+            out[name] = measure(off, member, m)
+        del off, member
+    out["verified"] = ("before timing, on every workload, for the first step at width 1 and for a later step at "
+                       "width 2 with half the keys done: the totals equal; d_out_cand equal to the gather; d_out_key "
+                       "equal to repeat_interleave's keys; the cursors equal")
     return out
 
 
@@ -1097,6 +1274,8 @@ def main():
                     help="rf_amd_found_per_key_ragged against found_compact + searchsorted + gather")
     ap.add_argument("--by-branch", dest="by_branch", action="store_true",
                     help="rf_amd_found_by_branch against torch.sort + gather + unique_consecutive")
+    ap.add_argument("--advance", action="store_true",
+                    help="rf_amd_found_advance against torch masks + cumsum + repeat_interleave + gather")
     ap.add_argument("--exists", action="store_true",
                     help="rf_amd_filter_set_exists_*_ragged against the ragged probe alone")
     ap.add_argument("--update", action="store_true",
@@ -1108,7 +1287,7 @@ def main():
     if args.out is None:
         name = "multiget" + ("_var" if args.var else "") + ("_ragged" if args.ragged else "") + \
             ("_routed" if args.routed else "") + ("_per_key" if args.per_key else "") + ("_by_branch" if args.by_branch else "") + \
-            ("_exists" if args.exists else "") + ".json"
+            ("_advance" if args.advance else "") + ("_exists" if args.exists else "") + ".json"
         name = "multiget_update.json" if args.update else "range_segments.json" if args.segments else name
         args.out = os.path.join(ROOT, "profiles", name)
     if not torch.cuda.is_available():
@@ -1190,10 +1369,12 @@ def main():
     def rng(v):
         return {"min": round(min(v), 4), "max": round(max(v), 4), "rounds": [round(x, 4) for x in v]}
 
-    if args.ragged or args.routed or args.per_key or args.exists or args.by_branch:
+    if args.ragged or args.routed or args.per_key or args.exists or args.by_branch or args.advance:
         del found_a, found_b, member
         kin = (d_bytes, d_offs) if args.var else (keys, 24)
-        if args.by_branch:
+        if args.advance:
+            out = advance(args, fset, eng, stream, kin, own, timed, rng)
+        elif args.by_branch:
             out = by_branch(args, fset, eng, stream, kin, own, timed, rng)
         elif args.exists:
             out = exists(args, fset, eng, stream, kin, timed, rng)
