@@ -27,6 +27,7 @@ extern "C" {
 #define RF_AMD_ENOMEM    12
 #define RF_AMD_ENODEV    19
 #define RF_AMD_EINVAL    22
+#define RF_AMD_ENOSPC    28  /* a well-formed edit that exceeds a range map's room */
 
 /* per-filter error bits reported in rf_amd_filter_info.error */
 #define RF_AMD_ERR_INDEX_OVERFLOW 1u /* > 4096 entries in one index (ref: fp_buffer overflow, :596) */
@@ -580,7 +581,8 @@ int rf_amd_range_map_route_var_keys(rf_amd_range_map *m, const uint8_t *d_bytes,
  * flat map, NULL arrays with count > 0 (h_ids may be NULL when every list is empty), an id >=
  * num_segments, a list longer than its segment's capacity, decreasing offsets. If the HIP
  * runtime refuses a launch the map is good only for destroy.
- * Boundaries and paths do not change in place: a leaf split or a new level makes a new map. */
+ * Boundaries and paths change in place only in a map created with room (below); a map made by
+ * rf_amd_range_map_create_segments has none, and a leaf split or a new level makes a new map. */
 int rf_amd_range_map_create_segments(rf_amd_engine *e, uint32_t num_ranges,
                                      const uint8_t *h_bound_bytes, const uint64_t *h_bound_off,
                                      const uint32_t *h_path, const uint64_t *h_path_off,
@@ -591,6 +593,70 @@ uint32_t rf_amd_range_map_num_segments(const rf_amd_range_map *m);
 int rf_amd_range_map_update_segments(rf_amd_range_map *m, const uint32_t *seg_id,
                                      const uint32_t *h_ids, const uint64_t *h_ids_off,
                                      uint32_t count, void *stream);
+/* ---- range maps that follow node splits: stream-ordered range and path edits -----------------
+ * Every flush into a full leaf ends in leaf_split (src/trunk.c:4789): m - 1 new pivot keys
+ * (leaf_split_select_pivots, leaf_split_init, :4710-4736) fall strictly inside one range, the
+ * parent replaces the child's pivot by one pivot per new leaf (flush_to_one_child, :5258-5340)
+ * -- each starting empty, inflight_bundle_start at the end (:5271-5275) -- and every new leaf
+ * receives the old leaf's bundles (trunk_node_receive_bundles). In the map's terms one range
+ * becomes m ranges, every later range moves up by m - 1, and each new range gets a path of its
+ * own. An index_split (:4977) moves no boundary and replaces the paths of a contiguous run of
+ * ranges. Segments in no path are legal, so the caller declares spare segments at create, fills
+ * them with update_segments, and the edit only names them.
+ *
+ * create_segments_room: the arguments of rf_amd_range_map_create_segments and the bounds of the
+ * map for its life: room->ranges the most ranges, room->bound_bytes the most boundary bytes,
+ * room->path_entries the most path entries, room->list_ids the most ids the flat list may need
+ * (the sum over ranges of their paths' capacities), room->max_list the largest capacity sum any
+ * path may ever have. rf_amd_range_map_max_list returns room->max_list, so pair_cap = n *
+ * max_list holds whatever edits arrive. EINVAL: everything create_segments refuses, a NULL room,
+ * a room smaller than the initial table in any field, room->max_list > 65,535. The image holds
+ * the boundaries and the paths twice (an edit reads one copy and writes the other), everything
+ * else once, all sized by room.
+ *
+ * split: range `range` becomes pieces >= 1 ranges. The pieces - 1 new boundaries are
+ * h_bound_bytes[h_bound_off[j] .. h_bound_off[j+1]) (pieces offsets; both NULL allowed with
+ * pieces == 1, which replaces the range's path only), strictly ascending under slice_lex_cmp,
+ * strictly above the range's lower boundary and strictly below its upper one (range 0 has no
+ * lower, range R - 1 no upper; a zero-length boundary can therefore only become the first of the
+ * map). New range i's path is h_path[h_path_off[i] .. h_path_off[i+1]) (pieces + 1 offsets).
+ * set_paths: the paths of ranges [first, first + count) are replaced likewise (count + 1
+ * offsets); count == 0 on a map with room is OK and touches nothing.
+ *
+ * Both are asynchronous on stream (NULL = the engine's) with the contract of update_segments:
+ * nothing is waited for, nothing allocated on the device, the host arrays are free on return.
+ * The new boundaries (with their 8-byte prefixes, computed on the host), offsets and paths
+ * travel in kernel arguments, in as many launches as they need, each reading one copy of the
+ * boundaries and paths and writing the other; the three launches that rewrite the flat table
+ * follow. A route call queued on stream before the call sees the old table and the old range
+ * numbering -- the copy it reads stays untouched until the next edit on that stream -- and one
+ * queued after it the new. rf_amd_range_map_num_ranges is the new R as soon as the call
+ * returns. The caller orders other streams against the call and serialises calls on one map.
+ * Every check is made before the first launch and a refused call changes nothing on the host or
+ * the device. EINVAL: a NULL map, a flat map or one without room, range >= R or first + count >
+ * R, pieces == 0, decreasing offsets, a boundary out of order or out of its range, a path entry
+ * >= num_segments, a path whose capacities sum to more than room->max_list, NULL arrays where
+ * needed. RF_AMD_ENOSPC: a well-formed call that exceeds room in ranges, boundary bytes, path
+ * entries or list ids. If the HIP runtime refuses a launch the map is good only for destroy.
+ * Out of scope: merging ranges, and growing past room (both make a new map). */
+typedef struct {
+  uint32_t ranges;
+  uint64_t bound_bytes;
+  uint64_t path_entries;
+  uint64_t list_ids;
+  uint32_t max_list;
+} rf_amd_range_room;
+int rf_amd_range_map_create_segments_room(rf_amd_engine *e, uint32_t num_ranges,
+                                          const uint8_t *h_bound_bytes, const uint64_t *h_bound_off,
+                                          const uint32_t *h_path, const uint64_t *h_path_off,
+                                          uint32_t num_segments, const uint32_t *h_seg_cap,
+                                          const uint32_t *h_seg_ids, const uint64_t *h_seg_off,
+                                          const rf_amd_range_room *room, rf_amd_range_map **out);
+int rf_amd_range_map_split(rf_amd_range_map *m, uint32_t range, uint32_t pieces,
+                           const uint8_t *h_bound_bytes, const uint64_t *h_bound_off,
+                           const uint32_t *h_path, const uint64_t *h_path_off, void *stream);
+int rf_amd_range_map_set_paths(rf_amd_range_map *m, uint32_t first, uint32_t count,
+                               const uint32_t *h_path, const uint64_t *h_path_off, void *stream);
 /* The engine's lookup server: single lookups -- routing_filter_lookup (src/routing_filter.h:
  * 87-92) and routing_filter_lookup_async states (:130-155) -- without a kernel launch per
  * call. A persistent wave (started on demand on a queue of its own, exiting after 400 us

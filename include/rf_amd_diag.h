@@ -116,6 +116,11 @@ uint32_t rf_amd_diag_range_seg_launch_ids(void);
 /* the flatten expands a range's list of at most this many ids by one thread and a longer one by
  * a wave: a test takes lists of exactly this length and of one id more */
 uint32_t rf_amd_diag_range_seg_thread_ids(void);
+/* the 32-bit words of new elements one launch of rf_amd_range_map_split / _set_paths carries: four
+ * per new boundary (its prefix and offset), one per four boundary bytes, two per new range (its
+ * path's offset) and one per path entry, kinds in that order, each kind rounded up on its own. An
+ * edit of one word more takes two launches. The splice honours rf_amd_diag_fanout_max_blocks. */
+uint32_t rf_amd_diag_range_splice_words(void);
 /* the keys of one tile of rf_amd_found_per_key / _ragged (the unit of their scratch and of their
  * grid-stride loops, which honour rf_amd_diag_fanout_max_blocks like the route kernels);
  * rf_amd_found_advance walks its keys in the same tiles and honours the same cap */

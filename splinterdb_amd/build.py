@@ -11,7 +11,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "librf_amd.so")
 LIB_STAMPS = os.path.join(HERE, "librf_amd_stamps.so")  # diagnostics: per-phase clock stamps
 SOURCES = ["rf_kernels.hip", "rf_range.hip", "rf_per_key.hip", "rf_by_branch.hip", "rf_advance.hip", "rf_engine.cpp"]
-HEADERS = ["rf_device.h", "rf_plan.h", "rf_batch_plan.h", "rf_set_plan.h", "rf_range_plan.h", "rf_range_seg_plan.h", "rf_per_key_plan.h", "rf_by_branch_plan.h", "rf_advance_plan.h", "rf_launch.h", "../../include/rf_amd.h", "../../include/rf_amd_diag.h"]
+HEADERS = ["rf_device.h", "rf_plan.h", "rf_batch_plan.h", "rf_set_plan.h", "rf_range_plan.h", "rf_range_seg_plan.h", "rf_range_split_plan.h", "rf_per_key_plan.h", "rf_by_branch_plan.h", "rf_advance_plan.h", "rf_launch.h", "../../include/rf_amd.h", "../../include/rf_amd_diag.h"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 

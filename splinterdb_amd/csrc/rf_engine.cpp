@@ -2429,7 +2429,9 @@ extern "C" int rf_amd_found_advance(rf_amd_engine* e, const uint64_t* d_key_off,
 // three launches over it and the caller's buffers (rf_range.hip). It holds no reference to any
 // set or batch, and nothing downstream reads it: the route output is a copy.
 // A map made from segments (rf_range_seg_plan.h) also keeps the segment sections' addresses, the
-// capacities for the validation of an update, and the host scratch of an update call.
+// capacities for the validation of an update, and the host scratch of an update call. One made
+// with room (rf_range_split_plan.h) keeps both copies of the structural sections by address and
+// the host state of its edits; dev and seg name the live copy.
 struct rf_amd_range_map {
   rf_amd_engine* eng = nullptr;
   uint32_t num_ranges = 0, max_list = 0;
@@ -2440,6 +2442,11 @@ struct rf_amd_range_map {
   RangeSegState seg_state;
   RangeSegUpdatePlan upd_plan;
   RangeSegUpdate upd_args{};
+  bool roomy = false;
+  RangeStructDev copy[2]{};
+  RangeSplitState split;
+  RangeSplicePlan splice_plan;
+  RangeSpliceArgs splice_args{};
 };
 
 // the image in one pool block by one copy on the engine stream, which is synchronised: the image
@@ -2506,6 +2513,39 @@ extern "C" int rf_amd_range_map_create_segments(rf_amd_engine* e, uint32_t num_r
   return 0;
 }
 
+extern "C" int rf_amd_range_map_create_segments_room(rf_amd_engine* e, uint32_t num_ranges,
+                                                     const uint8_t* h_bound_bytes, const uint64_t* h_bound_off,
+                                                     const uint32_t* h_path, const uint64_t* h_path_off,
+                                                     uint32_t num_segments, const uint32_t* h_seg_cap,
+                                                     const uint32_t* h_seg_ids, const uint64_t* h_seg_off,
+                                                     const rf_amd_range_room* room, rf_amd_range_map** out) {
+  if (!e) return fail(RF_AMD_ENODEV, "no engine");
+  if (!out) return fail(RF_AMD_EINVAL, "null out-param");
+  *out = nullptr;
+  RangeRoomPlan plan;
+  std::string msg;
+  if (int rc = plan_range_map_segments_room(num_ranges, h_bound_bytes, h_bound_off, h_path, h_path_off, num_segments,
+                                            h_seg_cap, h_seg_ids, h_seg_off, room, &plan, &msg))
+    return fail(rc, msg);
+  HIPCHK(hipSetDevice(e->device));
+  auto m = std::make_unique<rf_amd_range_map>();
+  m->segmented = m->roomy = true;
+  m->seg_state.init(h_seg_cap, num_segments);
+  m->split.init(*room, num_ranges, h_bound_bytes, h_bound_off, h_path, h_path_off, h_seg_cap);
+  if (int rc = range_map_upload(m.get(), e, plan)) return rc;
+  uint8_t* base = m->d_image.as<uint8_t>();
+  m->seg = range_seg_dev(plan, base);
+  m->copy[0] = range_struct_dev(plan, base, 0);
+  m->copy[1] = range_struct_dev(plan, base, 1);
+  m->upd_args.slots = m->seg.slots;
+  m->upd_args.slen = m->seg.slen;
+  m->upd_args.sbase = m->seg.sbase;
+  m->upd_args.scap = m->seg.scap;
+  m->upd_args.num_segments = num_segments;
+  *out = m.release();
+  return 0;
+}
+
 // Segment lists replaced in stream order: every entry is validated and the call cut into launches
 // on the host (rf_range_seg_plan.h) before the first launch; the scatter launches carry the ids
 // in their arguments, then the flatten rewrites the flat table the route kernels read. Nothing
@@ -2528,6 +2568,59 @@ extern "C" int rf_amd_range_map_update_segments(rf_amd_range_map* m, const uint3
     if (int rc = launch_rc("segment update", rf_launch_range_seg_scatter(st, &m->upd_args))) return rc;
   }
   return launch_rc("segment flatten", rf_launch_range_seg_flatten(st, &m->seg));
+}
+
+// An edit whose plan the host has accepted, in stream order: the splice launches read the copy
+// that was live and write the other, which the route launches and the flatten are given from here
+// on; then the flatten. The copy that route calls already queued read is not written before the
+// next edit. Nothing is waited for and nothing allocated; the call's host scratch lives in the map.
+static int range_map_splice(rf_amd_range_map* m, const uint8_t* h_bound_bytes, const uint64_t* h_bound_off,
+                            const uint32_t* h_path, const uint64_t* h_path_off, void* stream) {
+  HIPCHK(hipSetDevice(m->eng->device));
+  (void)hipGetLastError();
+  hipStream_t st = stream_of(m->eng, stream);
+  const RangeStructDev& to = m->copy[m->split.live];
+  m->splice_args.src = m->copy[m->split.live ^ 1u];
+  m->splice_args.dst = to;
+  m->num_ranges = m->dev.num_ranges = m->seg.num_ranges = m->splice_plan.e.r_new;
+  m->dev.prefix = to.prefix;
+  m->dev.boff = to.boff;
+  m->dev.bytes = to.bytes;
+  m->seg.poff = to.poff;
+  m->seg.path = to.path;
+  for (uint32_t l = 0; l < m->splice_plan.launches(); l++) {
+    range_splice_fill_launch(m->splice_plan, l, h_bound_bytes, h_bound_off, h_path, h_path_off, &m->splice_args);
+    if (int rc = launch_rc("range splice", rf_launch_range_splice(st, &m->splice_args))) return rc;
+  }
+  return launch_rc("segment flatten", rf_launch_range_seg_flatten(st, &m->seg));
+}
+
+static int range_map_roomy(const rf_amd_range_map* m) {
+  if (!m) return fail(RF_AMD_EINVAL, "null range map");
+  if (!m->segmented) return fail(RF_AMD_EINVAL, "a flat range map has no paths");
+  if (!m->roomy) return fail(RF_AMD_EINVAL, "a range map created without room");
+  return 0;
+}
+
+extern "C" int rf_amd_range_map_split(rf_amd_range_map* m, uint32_t range, uint32_t pieces,
+                                      const uint8_t* h_bound_bytes, const uint64_t* h_bound_off,
+                                      const uint32_t* h_path, const uint64_t* h_path_off, void* stream) {
+  if (int rc = range_map_roomy(m)) return rc;
+  std::string msg;
+  if (int rc = plan_range_split(&m->split, m->seg_state, range, pieces, h_bound_bytes, h_bound_off, h_path,
+                                h_path_off, &m->splice_plan, &msg))
+    return fail(rc, msg);
+  return range_map_splice(m, h_bound_bytes, h_bound_off, h_path, h_path_off, stream);
+}
+
+extern "C" int rf_amd_range_map_set_paths(rf_amd_range_map* m, uint32_t first, uint32_t count, const uint32_t* h_path,
+                                          const uint64_t* h_path_off, void* stream) {
+  if (int rc = range_map_roomy(m)) return rc;
+  if (count == 0 && first <= m->num_ranges) return 0;
+  std::string msg;
+  if (int rc = plan_range_set_paths(&m->split, m->seg_state, first, count, h_path, h_path_off, &m->splice_plan, &msg))
+    return fail(rc, msg);
+  return range_map_splice(m, nullptr, nullptr, h_path, h_path_off, stream);
 }
 
 // synchronises the device (route calls on a caller's stream may still read the image), as
@@ -2557,6 +2650,7 @@ extern "C" uint32_t rf_amd_range_map_num_segments(const rf_amd_range_map* m) {
 }
 extern "C" uint32_t rf_amd_diag_range_seg_launch_ids(void) { return RANGE_SEG_LAUNCH_IDS; }
 extern "C" uint32_t rf_amd_diag_range_seg_thread_ids(void) { return RANGE_SEG_THREAD_IDS; }
+extern "C" uint32_t rf_amd_diag_range_splice_words(void) { return RANGE_SPLICE_WORDS; }
 extern "C" uint64_t rf_amd_range_route_scratch_bytes(uint64_t n) { return range_route_scratch_bytes(n); }
 extern "C" uint32_t rf_amd_diag_range_lds_ranges(void) { return RANGE_LDS_RANGES; }
 extern "C" uint32_t rf_amd_diag_range_tile(void) { return RANGE_TILE; }

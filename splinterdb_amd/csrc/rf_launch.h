@@ -7,6 +7,7 @@
 #include "rf_plan.h"
 #include "rf_range_plan.h"
 #include "rf_range_seg_plan.h"
+#include "rf_range_split_plan.h"
 #include "rf_per_key_plan.h"
 #include "rf_by_branch_plan.h"
 #include "rf_advance_plan.h"
@@ -97,6 +98,9 @@ int rf_launch_range_seg_scatter(void* stream, const rf::RangeSegUpdate* a);
 // k_range_seg_len, k_range_scan, k_range_seg_emit: loff[0..R] and list rewritten from the
 // segments' current lists
 int rf_launch_range_seg_flatten(void* stream, const rf::RangeSegDev* d);
+// k_range_splice: one launch of a split or set_paths, from the structural copy a->src into
+// a->dst (rf_range_split_plan.h); the first launch of an edit (a->bulk) copies what it keeps
+int rf_launch_range_splice(void* stream, const rf::RangeSpliceArgs* a);
 // diagnostics (rf_amd_diag_fanout_max_blocks): a cap on the route and flatten kernels' grids; 0 =
 // none
 void rf_range_set_max_blocks(uint32_t blocks);

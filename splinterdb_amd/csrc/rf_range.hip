@@ -355,6 +355,19 @@ __global__ __launch_bounds__(RG_NT) void k_range_seg_emit(RangeSegDev d, uint64_
   }
 }
 
+// ---- maps that follow node splits (rf_range_split_plan.h) --------------------------------------
+// rf_amd_range_map_split / _set_paths: one launch per argument block. The structural sections
+// are kept twice; a launch reads the live copy and stores into the other one, so no thread
+// stores where another one of the launch loads, whatever the order of the workgroups. The first
+// launch of an edit copies what the edit keeps, each element placed by index arithmetic on the
+// host's splice points; every launch stores the new elements it carries in its arguments. The
+// flatten above follows, reading the copy just written.
+constexpr uint32_t RG_SPLICE_MAX_GRID = 1024;
+
+__global__ __launch_bounds__(RG_NT) void k_range_splice(RangeSpliceArgs a) {
+  range_splice_store(a, (uint64_t)blockIdx.x * RG_NT + threadIdx.x, (uint64_t)gridDim.x * RG_NT);
+}
+
 // diagnostics (rf_amd_diag_fanout_max_blocks): a cap on the grids below, so that a route call
 // over a few tiles runs every grid-stride loop more than once per workgroup; 0 = none
 std::atomic<uint32_t> g_range_max_blocks{0};
@@ -375,6 +388,17 @@ extern "C" int rf_launch_range_seg_scatter(void* stream, const rf::RangeSegUpdat
   if (a->npieces == 0) return 0;
   if (a->npieces > RANGE_SEG_WORDS / RANGE_SEG_PIECE_WORDS) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(k_range_seg_scatter, dim3(1), dim3(RG_NT), 0, (hipStream_t)stream, *a);
+  return launch_status();
+}
+
+extern "C" int rf_launch_range_splice(void* stream, const rf::RangeSpliceArgs* a) {
+  // a launch that copies nothing stores at most its RANGE_SPLICE_WORDS words (bytes: four a word)
+  const uint64_t elems = a->bulk ? range_splice_bulk_elems(a->e) : 4ull * RANGE_SPLICE_WORDS;
+  uint64_t nblk = (elems + RG_NT - 1) / RG_NT;
+  if (nblk > RG_SPLICE_MAX_GRID) nblk = RG_SPLICE_MAX_GRID;
+  const uint32_t cap = g_range_max_blocks.load(std::memory_order_relaxed);
+  if (cap && nblk > cap) nblk = cap;
+  hipLaunchKernelGGL(k_range_splice, dim3((uint32_t)nblk), dim3(RG_NT), 0, (hipStream_t)stream, *a);
   return launch_status();
 }
 

@@ -23,6 +23,7 @@ STATUS_OK = 0
 STATUS_NO_MEMORY = 12
 STATUS_NO_DEVICE = 19
 STATUS_BAD_PARAM = 22
+STATUS_NO_SPACE = 28  # RF_AMD_ENOSPC: an edit that exceeds a range map's room
 MAX_FILTERS = 32  # src/routing_filter.h:25
 ROUTING_NOT_FOUND = 0xFFFF  # src/routing_filter.h:26
 
@@ -73,6 +74,8 @@ EXPORTED = [
     "rf_amd_diag_range_tile", "rf_amd_diag_range_lds_ranges",
     "rf_amd_range_map_create_segments", "rf_amd_range_map_num_segments", "rf_amd_range_map_update_segments",
     "rf_amd_diag_range_seg_launch_ids", "rf_amd_diag_range_seg_thread_ids",
+    "rf_amd_range_map_create_segments_room", "rf_amd_range_map_split", "rf_amd_range_map_set_paths",
+    "rf_amd_diag_range_splice_words",
     "rf_amd_found_per_key_scratch_bytes", "rf_amd_found_per_key", "rf_amd_found_per_key_ragged",
     "rf_amd_diag_per_key_tile",
     "rf_amd_filter_set_exists_keys", "rf_amd_filter_set_exists_var_keys", "rf_amd_filter_set_exists_hashes",
@@ -110,6 +113,13 @@ class RfFilterInfo(ctypes.Structure):
 class RfImage(ctypes.Structure):
     _fields_ = [("info", RfFilterInfo), ("pages", ctypes.POINTER(ctypes.c_uint8)),
                 ("slots", ctypes.POINTER(ctypes.c_uint64))]
+
+
+class RangeRoom(ctypes.Structure):
+    """rf_amd_range_room: what a range map that follows splits may grow to"""
+    _fields_ = [("ranges", ctypes.c_uint32), ("bound_bytes", ctypes.c_uint64),
+                ("path_entries", ctypes.c_uint64), ("list_ids", ctypes.c_uint64),
+                ("max_list", ctypes.c_uint32)]
 
 
 _lib = None
@@ -308,6 +318,12 @@ def load_library(build_if_missing=True):
     L.rf_amd_diag_range_seg_launch_ids.restype = u32
     L.rf_amd_diag_range_seg_thread_ids.argtypes = []
     L.rf_amd_diag_range_seg_thread_ids.restype = u32
+    L.rf_amd_range_map_create_segments_room.argtypes = [vp, u32, vp, vp, vp, vp, u32, vp, vp, vp,
+                                                        ctypes.POINTER(RangeRoom), ctypes.POINTER(vp)]
+    L.rf_amd_range_map_split.argtypes = [vp, u32, u32, vp, vp, vp, vp, vp]
+    L.rf_amd_range_map_set_paths.argtypes = [vp, u32, u32, vp, vp, vp]
+    L.rf_amd_diag_range_splice_words.argtypes = []
+    L.rf_amd_diag_range_splice_words.restype = u32
     L.rf_amd_found_per_key_scratch_bytes.argtypes = [u64]
     L.rf_amd_found_per_key_scratch_bytes.restype = u64
     L.rf_amd_found_per_key.argtypes = [vp, vp, vp, u32, u64, vp, vp, vp, u64, vp, vp, vp]
@@ -1820,6 +1836,38 @@ def range_segment_lists(paths, seg_lists):
     return [[i for s in path for i in seg_lists[s]] for path in paths]
 
 
+def diag_range_splice_words() -> int:
+    """the 32-bit words of new elements one launch of RangeMap.split / set_paths carries
+    (rf_amd_diag_range_splice_words): see range_splice_words"""
+    return int(load_library().rf_amd_diag_range_splice_words())
+
+
+def range_splice_words(boundaries, paths) -> int:
+    """the argument words the new elements of a split (set_paths: no boundaries) take: four per
+    boundary, one per four boundary bytes, two per path and one per path entry. An edit of at
+    most diag_range_splice_words() words is one splice launch."""
+    return (4 * len(boundaries) + (sum(len(b) for b in boundaries) + 3) // 4 + 2 * len(paths)
+            + sum(len(p) for p in paths))
+
+
+def range_split_host(boundaries, paths, r, new_boundaries, new_paths):
+    """Host model of RangeMap.split as list surgery: the (boundaries, paths) of the map after
+    range r has become len(new_paths) ranges. Feed the result to range_segment_lists and
+    range_route_host."""
+    if len(new_boundaries) != len(new_paths) - 1:
+        raise ValueError("m pieces take m - 1 boundaries")
+    boundaries, paths = [bytes(b) for b in boundaries], [list(p) for p in paths]
+    return (boundaries[:r] + [bytes(b) for b in new_boundaries] + boundaries[r:],
+            paths[:r] + [list(p) for p in new_paths] + paths[r + 1:])
+
+
+def range_set_paths_host(paths, first, new_paths):
+    """Host model of RangeMap.set_paths: the paths after those of [first, first + len(new_paths))
+    have been replaced"""
+    paths = [list(p) for p in paths]
+    return paths[:first] + [list(p) for p in new_paths] + paths[first + len(new_paths):]
+
+
 def _csr(seqs, dtype):
     """(flat array of `dtype` with one spare element, uint64 offsets) of a list of sequences"""
     off = np.zeros(len(seqs) + 1, dtype=np.uint64)
@@ -1836,7 +1884,8 @@ class RangeMap:
     boundaries = the R - 1 boundary keys as `bytes`, strictly ascending in `bytes` order; lists =
     R sequences of member ids (of whatever FilterSet the caller probes), each of at most 65,535.
     Range r holds the keys k with boundaries[r-1] <= k < boundaries[r]. A map made this way is
-    immutable; one made by from_segments follows the trunk through update_segments."""
+    immutable; one made by from_segments follows the trunk through update_segments, and one made
+    there with room= follows node splits through split and set_paths. num_ranges is the current R."""
 
     def __init__(self, boundaries, lists, engine=None):
         self.engine = engine or default_engine()
@@ -1869,12 +1918,15 @@ class RangeMap:
         return np.frombuffer(b"".join(boundaries) + b"\0", dtype=np.uint8), boff
 
     @classmethod
-    def from_segments(cls, boundaries, paths, seg_lists, seg_caps=None, engine=None):
+    def from_segments(cls, boundaries, paths, seg_lists, seg_caps=None, engine=None, room=None):
         """rf_amd_range_map_create_segments: R = len(paths) ranges; paths[r] = range r's segment
         ids, root to leaf; seg_lists[s] = segment s's initial ids; seg_caps[s] = the ids it has
         room for (None: its initial length). Range r's list is the concatenation of its path's
         segments' current lists (range_segment_lists); max_list is the largest sum of a path's
-        capacities, which no update can exceed."""
+        capacities, which no update can exceed.
+        room (rf_amd_range_map_create_segments_room): a RangeRoom or a dict of its fields --
+        ranges, bound_bytes, path_entries, list_ids, max_list -- the most the map may grow to by
+        split and set_paths; max_list is then room's."""
         self = cls.__new__(cls)
         self.h = None
         self.engine = engine or default_engine()
@@ -1887,9 +1939,15 @@ class RangeMap:
             raise ValueError("seg_caps and seg_lists differ in length")
         caps = np.ascontiguousarray(np.append(np.asarray(caps, dtype=np.uint32), np.uint32(0)))
         h = ctypes.c_void_p()
-        _check(load_library().rf_amd_range_map_create_segments(
-            self.engine.h, R, bbytes.ctypes.data, boff.ctypes.data, path.ctypes.data, poff.ctypes.data, S,
-            caps.ctypes.data, ids.ctypes.data, soff.ctypes.data, ctypes.byref(h)))
+        args = (self.engine.h, R, bbytes.ctypes.data, boff.ctypes.data, path.ctypes.data, poff.ctypes.data, S,
+                caps.ctypes.data, ids.ctypes.data, soff.ctypes.data)
+        if room is None:
+            _check(load_library().rf_amd_range_map_create_segments(*args, ctypes.byref(h)))
+        else:
+            room = room if isinstance(room, RangeRoom) else RangeRoom(**room)
+            if R == 1:  # the map every trunk starts as: no boundary arrays at all
+                args = args[:2] + (None, None) + args[4:]
+            _check(load_library().rf_amd_range_map_create_segments_room(*args, ctypes.byref(room), ctypes.byref(h)))
         self.h = h
         self.num_ranges = R
         self.num_segments = int(load_library().rf_amd_range_map_num_segments(h))
@@ -1909,6 +1967,34 @@ class RangeMap:
         _check(load_library().rf_amd_range_map_update_segments(
             self.h, ids.ctypes.data if ids.size else None, flat.ctypes.data if ids.size else None,
             off.ctypes.data if ids.size else None, ids.size, _stream(stream)))
+
+    def split(self, range, boundaries, paths, stream=None):
+        """rf_amd_range_map_split on a map made with room: range `range` becomes len(paths)
+        ranges cut by the len(paths) - 1 new `boundaries` (strictly inside the range, ascending),
+        with those paths; one path and no boundary replaces the range's path only. In stream
+        order and without a host wait, like update_segments: a route call queued before it sees
+        the old table and range numbers, one queued after it the new. num_ranges is the new R on
+        return. A call that exceeds the room raises with code STATUS_NO_SPACE and changes nothing."""
+        paths = list(paths)
+        boundaries = [bytes(b) for b in boundaries]
+        if paths and len(boundaries) != len(paths) - 1:
+            raise ValueError("m pieces take m - 1 boundaries")
+        boff = np.zeros(len(boundaries) + 1, dtype=np.uint64)
+        np.cumsum(np.array([len(b) for b in boundaries], dtype=np.uint64), out=boff[1:])
+        bbytes = np.frombuffer(b"".join(boundaries) + b"\0", dtype=np.uint8)
+        path, poff = _csr(paths, np.uint32)
+        _check(load_library().rf_amd_range_map_split(self.h, range, len(paths), bbytes.ctypes.data, boff.ctypes.data,
+                                                     path.ctypes.data, poff.ctypes.data, _stream(stream)))
+        self.num_ranges = int(load_library().rf_amd_range_map_num_ranges(self.h))
+
+    def set_paths(self, first, paths, stream=None):
+        """rf_amd_range_map_set_paths on a map made with room: the paths of ranges [first, first +
+        len(paths)) are replaced, in stream order like split -- an index split's outcome, or over
+        all ranges a new root level"""
+        paths = list(paths)
+        path, poff = _csr(paths, np.uint32)
+        _check(load_library().rf_amd_range_map_set_paths(self.h, first, len(paths), path.ctypes.data,
+                                                         poff.ctypes.data, _stream(stream)))
 
     def close(self):
         if getattr(self, "h", None):

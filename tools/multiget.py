@@ -62,6 +62,20 @@ through E.RangeMap(...) + close_on. A route call of 2^20 24-byte keys is timed o
 before and after every update and on the flat map. Both ways' route output after the same change
 is compared over all keys before anything is timed. Default output: profiles/range_segments.json.
 
+--split: what a leaf split does to a resident range map, two ways, on the table of --segments with
+16 spare segments: one leaf splits into 2 and into 8. (split) on a map created with room
+(E.RangeMap.from_segments(..., room=...)): rf_amd_range_map_update_segments of the new leaves'
+spare segments, then rf_amd_range_map_split -- one splice launch and the three of the flatten.
+(rebuild) what the parent commit must do: rf_amd_range_map_create_segments of the new table and
+rf_amd_range_map_destroy_on of the old map. Reported per way, median, minimum and maximum over the
+rounds, a fresh pair of maps each: the host wall time until the calls return (arrays built
+beforehand) and the wall time until the stream has drained. A route call of 2^20 24-byte keys is
+timed on both maps after the event: the same table, with and without room. Both ways' route
+output is compared over all keys before anything is timed. Conditions: the split's median to a
+drained stream below the rebuild's by more than the rebuild's round-to-round spread; the roomy
+map's route median not above the roomless map's by more than that one's spread. Default output:
+profiles/range_split.json.
+
 --per-key: the step behind the probe, two ways, on the --ragged lists and on the CSR that a route
 call writes for a map of R = 4,096 ranges with such lists (with --var: variable-length keys). What a
 consumer of the candidates needs is each record's member id and key. (parent_path) what a caller had:
@@ -100,6 +114,7 @@ method and the same condition as --per-key. Default output: profiles/multiget_ex
                                                [--out profiles/multiget.json]
     timeout -k 10 300 python tools/multiget.py --update --filters 1024 --keys 4096
     timeout -k 10 300 python tools/multiget.py --segments
+    timeout -k 10 300 python tools/multiget.py --split
 """
 import argparse
 import json
@@ -1258,6 +1273,190 @@ def segments_mode(args):
     eng.close()
 
 
+def split_mode(args):
+    """--split: a leaf split on a resident range map, two ways; see the module docstring"""
+    import ctypes
+    import statistics
+    import time
+
+    import numpy as np
+    R, fan, n, cap = SEG_R, SEG_FAN, SEG_N, 8
+    dev = torch.device("cuda:0")
+    eng = E.Engine(0)
+    L = E.load_library()
+    stream = torch.cuda.Stream(device=dev)
+    st = stream.cuda_stream
+    hr = np.random.default_rng(23)
+    widths = [fan, fan * fan, R, R]
+    first = np.concatenate([[0], np.cumsum(widths)]).tolist()
+    spare = first[-1]          # 8 spare pivot segments of the parent, then 8 spare leaves
+    S = spare + 16
+    paths = [[first[0] + r // (R // widths[0]), first[1] + r // (R // widths[1]), first[2] + r, first[3] + r]
+             for r in range(R)]
+    seg_lists = [hr.integers(0, 1024, size=int(hr.integers(1, cap + 1))).tolist() for _ in range(spare)] + [[]] * 16
+    caps = np.full(S + 1, cap, dtype=np.uint32)
+    pool = sorted({bytes(b) for b in hr.integers(0, 256, size=(R + 64, 24), dtype=np.uint8)})
+    bounds = [pool[i] for i in sorted(hr.choice(len(pool), size=R - 1, replace=False))]
+    leaf = R // 2 + 5          # the leaf that splits
+    room = E.RangeRoom(ranges=R + 64, bound_bytes=24 * (R + 64), path_entries=4 * (R + 64),
+                       list_ids=4 * cap * (R + 64), max_list=4 * cap)
+    pair_cap = n * 4 * cap
+    with torch.cuda.stream(stream):
+        g = torch.Generator(device=dev)
+        g.manual_seed(7)
+        keys = torch.randint(0, 256, (n, 24), device=dev, generator=g, dtype=torch.uint8).contiguous()
+        outs = [(torch.zeros(n, dtype=torch.int32, device=dev), torch.zeros(n + 1, dtype=torch.int64, device=dev),
+                 torch.zeros(pair_cap, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int64, device=dev))
+                for _ in range(2)]
+        scratch = torch.zeros(E.range_route_scratch_bytes(n) // 8, dtype=torch.int64, device=dev)
+    stream.synchronize()
+
+    def route(h, out):
+        E._check(L.rf_amd_range_map_route_keys(h, keys.data_ptr(), 24, n, out[0].data_ptr(), out[1].data_ptr(),
+                                               out[2].data_ptr(), pair_cap, out[3].data_ptr(), scratch.data_ptr(), st))
+
+    def c_table(bounds, paths, lists):
+        """a segmented table in the C create's form, built before anything is timed"""
+        Rt = len(paths)
+        boff = np.zeros(Rt, dtype=np.uint64)
+        np.cumsum(np.array([len(b) for b in bounds], dtype=np.uint64), out=boff[1:])
+        path, poff = E._csr(paths, np.uint32)
+        ids, soff = E._csr(lists, np.uint32)
+        return (Rt, np.frombuffer(b"".join(bounds) + b"\0", dtype=np.uint8), boff, path, poff, ids, soff)
+
+    def create(t, with_room):
+        h = ctypes.c_void_p()
+        a = (eng.h, t[0], t[1].ctypes.data, t[2].ctypes.data, t[3].ctypes.data, t[4].ctypes.data, S, caps.ctypes.data,
+             t[5].ctypes.data, t[6].ctypes.data)
+        if with_room:
+            E._check(L.rf_amd_range_map_create_segments_room(*a, ctypes.byref(room), ctypes.byref(h)))
+        else:
+            E._check(L.rf_amd_range_map_create_segments(*a, ctypes.byref(h)))
+        return h
+
+    base = c_table(bounds, paths, seg_lists)
+    events = {}
+    for m in (2, 8):  # the leaf splits into m: m - 1 new boundaries between its own
+        lo, hi = bounds[leaf - 1], bounds[leaf]
+        span = int.from_bytes(hi, "big") - int.from_bytes(lo, "big")
+        nb = [(int.from_bytes(lo, "big") + span * (j + 1) // m).to_bytes(24, "big") for j in range(m - 1)]
+        assert lo < nb[0] and nb[-1] < hi and nb == sorted(set(nb))
+        new_paths = [paths[leaf][:2] + [spare + j, spare + 8 + j] for j in range(m)]
+        lists = list(seg_lists)
+        for j in range(m):  # the parent's new pivots start empty; each new leaf receives the old leaf's bundles
+            lists[spare + 8 + j] = seg_lists[first[3] + leaf]
+        nbounds, npaths = E.range_split_host(bounds, paths, leaf, nb, new_paths)
+        sid = np.arange(spare + 8, spare + 8 + m, dtype=np.uint32)
+        sids, sidoff = E._csr([lists[s] for s in sid], np.uint32)
+        sb = np.frombuffer(b"".join(nb) + b"\0", dtype=np.uint8)
+        sboff = (np.arange(m, dtype=np.uint64) * np.uint64(24))
+        spath, spoff = E._csr(new_paths, np.uint32)
+        events[m] = dict(new=c_table(nbounds, npaths, lists), nbounds=nbounds, npaths=npaths, lists=lists,
+                         split=(sid, sids, sidoff, sb, sboff, spath, spoff))
+
+    def way_split(h, m):
+        sid, sids, sidoff, sb, sboff, spath, spoff = events[m]["split"]
+        E._check(L.rf_amd_range_map_update_segments(h, sid.ctypes.data, sids.ctypes.data, sidoff.ctypes.data, m, st))
+        E._check(L.rf_amd_range_map_split(h, leaf, m, sb.ctypes.data, sboff.ctypes.data, spath.ctypes.data,
+                                          spoff.ctypes.data, st))
+
+    def way_rebuild(old, m):
+        h = create(events[m]["new"], False)
+        E._check(L.rf_amd_range_map_destroy_on(old, st))
+        return h
+
+    # both ways' route output after the same event, compared before anything is timed
+    for m in (2, 8):
+        a = create(base, True)
+        way_split(a, m)
+        b = way_rebuild(create(base, False), m)
+        route(a, outs[0])
+        route(b, outs[1])
+        stream.synchronize()
+        tot = int(outs[0][3].item())
+        assert L.rf_amd_range_map_num_ranges(a) == R + m - 1 == L.rf_amd_range_map_num_ranges(b)
+        assert tot == int(outs[1][3].item()) and torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
+        assert torch.equal(outs[0][2][:tot], outs[1][2][:tot]), "the two ways' ids differ"
+        sample = hr.choice(n, size=1 << 14, replace=False)
+        hk = keys[torch.from_numpy(sample).to(dev)].cpu().numpy()
+        flat = E.range_segment_lists(events[m]["npaths"], events[m]["lists"])
+        mirror = E.range_route_host(events[m]["nbounds"], flat, [bytes(x) for x in hk])[0]
+        assert np.array_equal(mirror, outs[0][0].cpu().numpy().view(np.uint32)[sample]), "ranges differ from the mirror"
+        L.rf_amd_range_map_destroy(a)
+        L.rf_amd_range_map_destroy(b)
+
+    def timed(fn):
+        """(host microseconds until the call returns, microseconds until the stream has drained)"""
+        stream.synchronize()
+        t0 = time.perf_counter()
+        r = fn()
+        t1 = time.perf_counter()
+        stream.synchronize()
+        return (t1 - t0) * 1e6, (time.perf_counter() - t0) * 1e6, r
+
+    def timed_route(h):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(stream)
+        route(h, outs[0])
+        b.record(stream)
+        stream.synchronize()
+        return a.elapsed_time(b)
+
+    def stats(v):
+        return {"median": round(statistics.median(v), 4), "min": round(min(v), 4), "max": round(max(v), 4),
+                "rounds": [round(x, 4) for x in v]}
+
+    out_events = {}
+    for m in (2, 8):
+        t = {k: [] for k in ("split_host_us", "split_drained_us", "rebuild_host_us", "rebuild_drained_us",
+                             "route_roomy_ms", "route_parent_ms")}
+        for r in range(args.warmup + args.rounds):
+            a = create(base, True)
+            old = create(base, False)
+            sh, sd, _ = timed(lambda: way_split(a, m))
+            rh, rd, b = timed(lambda: way_rebuild(old, m))
+            ra, rb = timed_route(a), timed_route(b)  # the same table: a roomy map, and the parent's map
+            if r >= args.warmup:
+                for name, v in (("split_host_us", sh), ("split_drained_us", sd), ("rebuild_host_us", rh),
+                                ("rebuild_drained_us", rd), ("route_roomy_ms", ra), ("route_parent_ms", rb)):
+                    t[name].append(v)
+            L.rf_amd_range_map_destroy(a)
+            L.rf_amd_range_map_destroy(b)
+        s = {k: stats(v) for k, v in t.items()}
+        spread = s["rebuild_drained_us"]["max"] - s["rebuild_drained_us"]["min"]
+        rspread = s["route_parent_ms"]["max"] - s["route_parent_ms"]["min"]
+        s["split_below_rebuild_by_more_than_its_spread"] = bool(
+            s["split_drained_us"]["median"] < s["rebuild_drained_us"]["median"] - spread)
+        s["route_roomy_within_parent_spread"] = bool(
+            s["route_roomy_ms"]["median"] <= s["route_parent_ms"]["median"] + rspread)
+        s["splice_launches"] = -(-E.range_splice_words([b"x" * 24] * (m - 1), [[0] * 4] * m) // E.diag_range_splice_words())
+        out_events["pieces_%d" % m] = s
+    out = {
+        "what": ("one leaf of a trunk-shaped range map (R leaves, paths of 4 segments, fan-out 16 per level, lists of "
+                 "1 to 8 ids, capacity 8) splits into 2 and into 8, two ways on one stream: (split) on a map created "
+                 "with room, rf_amd_range_map_update_segments of the new leaves' spare segments, then "
+                 "rf_amd_range_map_split; (rebuild) what a map without room needs: rf_amd_range_map_create_segments of "
+                 "the new table + rf_amd_range_map_destroy_on of the old map. host_us: wall time until the C calls "
+                 "return, their arrays built beforehand; drained_us: wall time from before the calls until the stream, "
+                 "idle at the start, has drained. route_*: one rf_amd_range_map_route_keys of n 24-byte keys by HIP "
+                 "events on the two maps after the event -- the same table; the route kernels and the roomless map "
+                 "are the parent commit's. A fresh pair of maps per round; median, minimum and maximum over the rounds"),
+        "config": {"ranges": R, "segments": S, "fan_out": fan, "path_segments": 4, "capacity": cap, "n": n,
+                   "key_len": 24, "leaf": leaf, "rounds": args.rounds, "warmup": args.warmup,
+                   "splice_words_per_launch": E.diag_range_splice_words()},
+        **out_events,
+        "verified": ("after each event both ways' route output equal (ranges, offsets, ids, total) over all n keys; "
+                     "ranges equal E.range_route_host over the edited model on 2^14 keys"),
+        "device": torch.cuda.get_device_name(0),
+    }
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as fh:
+        json.dump(out, fh, indent=1)
+        fh.write("\n")
+    print(json.dumps(out))
+    eng.close()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--filters", type=int, default=64)
@@ -1282,6 +1481,8 @@ def main():
                     help="member updates of a resident set against destroy + create of the whole set")
     ap.add_argument("--segments", action="store_true",
                     help="a segment update of a range map against the rebuild of a flat one")
+    ap.add_argument("--split", action="store_true",
+                    help="a leaf split on a range map with room against the rebuild of a segmented one")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
@@ -1289,6 +1490,7 @@ def main():
             ("_routed" if args.routed else "") + ("_per_key" if args.per_key else "") + ("_by_branch" if args.by_branch else "") + \
             ("_advance" if args.advance else "") + ("_exists" if args.exists else "") + ".json"
         name = "multiget_update.json" if args.update else "range_segments.json" if args.segments else name
+        name = "range_split.json" if args.split else name
         args.out = os.path.join(ROOT, "profiles", name)
     if not torch.cuda.is_available():
         sys.exit("multiget.py measures on the GPU: no HIP device")
@@ -1296,6 +1498,8 @@ def main():
         return update_mode(args)
     if args.segments:
         return segments_mode(args)
+    if args.split:
+        return split_mode(args)
     F, nk, n, Kf = args.filters, args.keys, args.n, args.k
     assert 1 <= F <= 64, "one value per filter: at most 64 filters"
     dev = torch.device("cuda:0")
